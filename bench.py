@@ -31,7 +31,17 @@ Per-GPU work is fixed as N grows (weak scaling). The model starts from zero
 (random-init equivalent for a linear model); the JSON reports the fraction
 of timed samples that updated it.
 
-Usage: python bench.py --gpus N --steps K --warmup W
+A plain run sets up, warms up, times the K steps and prints the result line
+(train throughput, ms_per_step). ``--full`` adds the secondary records after
+the timed steps: held-out accuracy and classify latency, the exact mode, a
+bf16 W table, the worst-case stream, the CPU baseline, the served paths and
+the engine records (N > 1: the distributed engine records); without it those
+fields of the result line are null. ``--dump-outputs DIR`` writes what the
+last timed step computed as float .npy files (see dump_outputs); the streams
+are seeded, so two runs with the same arguments train on the same bytes and
+write the same files.
+
+Usage: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
        (N > 1: launched by torch.distributed.run, one process per GPU; without
        WORLD_SIZE in the environment this script launches the N ranks itself)
 """
@@ -1163,11 +1173,126 @@ def _mix_summary(log: list) -> dict:
             "latency_ms_max": lat[-1] if lat else None}
 
 
+DUMP_TABLE_BYTES = 16_000_000     # per model table in --dump-outputs (everything together stays below 64 MB)
+DUMP_BATCH_VALUES = 2_000_000     # feature slots of the last batch written at most
+
+
+def _last_scan_batch(clf) -> dict:
+    """what the GPU request scan and fv_hash (csrc/hip/scan.hip, fv_hash.hip)
+    made of the last train batch: label ids, CSR row pointers, hashed
+    feature indices and values (FeaturePipeline.last_scan_batch). The leading
+    samples whose slots fit DUMP_BATCH_VALUES; nothing when the last batch
+    went through the host scanner."""
+    pipe = getattr(clf, "pipe", None)
+    b = pipe.last_scan_batch() if pipe is not None and clf.gpu else None
+    if b is None:
+        return {}
+    row_ptr = b.row_ptr[:b.n + 1].cpu().numpy()
+    m = int(np.searchsorted(row_ptr, DUMP_BATCH_VALUES, side="right")) - 1
+    nnz = int(row_ptr[m])
+    fidx = b.fidx[:nnz].cpu().numpy()
+    fval = b.fval[:nnz].cpu().numpy()
+    return {"last_batch_row_ptr": row_ptr[:m + 1].astype(np.float64),
+            "last_batch_labels": b.labels[:m].cpu().numpy().astype(np.float32),
+            "last_batch_fidx": fidx.astype(np.float32),                    # below 2^24: exact
+            "last_batch_fval": np.where(fidx >= 0, fval, 0).astype(np.float32)}   # (idx -1: slot not emitted)
+
+
+def _heldout_request(args) -> tuple[list, bytes]:
+    """a fixed held-out synthetic request: (labeled items, classify body)"""
+    test = make_requests(random.Random(99), 1, 2048, args.labels, args.str_features,
+                         args.num_features, args.vocab)[0]
+    items = msgpack.unpackb(test, raw=False)
+    return items, msgpack.packb([d for _, d in items], use_bin_type=False)
+
+
+def _model_arrays(clf, updated: int, scores: list, prefix: str = "") -> dict:
+    """a model as dump arrays: W and P (all rows, or a fixed seeded sample of
+    them - the same rows in every run, their numbers in rows.npy - when a
+    table is larger than DUMP_TABLE_BYTES), the number of samples that
+    updated it and its scores on the held-out request"""
+    W, P = clf._host_tables()
+    H = W.shape[0]
+    nrows = min(H, max(1, DUMP_TABLE_BYTES // (W.shape[1] * 4)))
+    rows = np.arange(H) if nrows == H else np.sort(np.random.default_rng(20240).choice(H, nrows, replace=False))
+    out = {"rows": rows.astype(np.float64), prefix + "W": np.ascontiguousarray(W[rows], dtype=np.float32),
+           prefix + "samples_updated": np.asarray([updated], np.float64),
+           prefix + "heldout_scores": np.asarray(scores, np.float32)}
+    if P is not None:
+        out[prefix + "P"] = np.ascontiguousarray(P[rows], dtype=np.float32)
+    return out
+
+
+def serial_probe(args, cfg, device, arena, body: bytes) -> dict:
+    """The lock-free update modes (atomic, hogwild) leave a model that depends
+    on how the concurrent streams interleaved, different in every run, so
+    the dump cannot hold it. In its place: a fresh model of the headline's
+    configuration (method, parameters, W storage) trained by the same scan,
+    hash and train kernels (csrc/hip/linear.hip) on the last timed batch with
+    one request a call - a single stream, whose samples apply in order - and
+    written as serial_W / serial_P / serial_samples_updated /
+    serial_heldout_scores. A change to the update arithmetic, to how W or P
+    are stored or to which samples update shows there."""
+    from jubatus_amd.fv_converter.converter import DatumToFvConverter
+    from jubatus_amd.models.classifier import LinearClassifier
+    clf = LinearClassifier(cfg["method"], cfg["parameter"], DatumToFvConverter(cfg["converter"]),
+                           device=device, concurrent_update=args.update_mode, weight_dtype=args.weight_dtype)
+    for y in range(args.labels):
+        clf.set_label(f"label{y}")
+    offs = np.asarray(arena.offs, np.int64)
+    lens = np.asarray(arena.lens, np.int64)
+    for i in range(offs.size):
+        clf.train_arena(arena, offs[i:i + 1], lens[i:i + 1])
+    clf.synchronize()
+    if device is not None:
+        clf.pipe.check_errors()
+    scores = [[v for _, v in r] for r in clf.classify_requests([body])]
+    return _model_arrays(clf, clf.train_stats()["updated"], scores, "serial_")
+
+
+def dump_outputs(path: str, clf, shape: list, step_samples: list, last_batch: dict, trained: int,
+                 model: dict) -> None:
+    """--dump-outputs: what the last timed step computed, as float32 /
+    float64 .npy files that are the same in every run with the same
+    arguments: the run's shape (batches per step - which follows the host's
+    free memory unless --batches-per-step is given -, steps), the sample
+    counts the last step's train calls returned, the samples trained in the
+    timed steps, the label counts, the scanned and hashed last batch (GPU
+    scan path) and ``model``: the timed steps' model where the update order
+    is defined (the exact mode, the host engine; one rank: _model_arrays),
+    else the serial probe of the train kernel (serial_probe)."""
+    os.makedirs(path, exist_ok=True)
+    out = {"run_shape": np.asarray(shape, np.float64),
+           "step_samples": np.asarray(step_samples, np.float64),
+           "samples_trained": np.asarray([trained], np.float64),
+           "label_counts": np.asarray([c for _, c in sorted(clf.get_labels().items())], np.float64)}
+    out.update(last_batch)
+    out.update(model)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also measure the secondary records: held-out "
+                         "accuracy and classify latency, exact mode / bf16 W / worst case / CPU baseline, "
+                         "the served paths and the engine records (N > 1: the distributed engine records). "
+                         "Without it only the headline is measured and those records are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (rank 0) as DIR/<name>.npy, "
+                         "the same in every run: the run's shape (batches per step, steps: give "
+                         "--batches-per-step where the host's free memory may change the default), the sample "
+                         "counts its train calls returned, the trained count, the label counts, the last batch "
+                         "as scanned and hashed on the GPU; with --update-mode exact or --device cpu on one "
+                         "rank the model (W, P: a fixed seeded sample of the rows when large, row numbers in "
+                         "rows.npy), the updated count and the scores on a fixed held-out request. The "
+                         "lock-free update modes leave a model that differs from run to run; there the same "
+                         "arrays of a fresh model trained on the last batch one request a call (in order) "
+                         "are written as serial_*")
     ap.add_argument("--requests", type=int, default=1024, help="concurrent train requests per batch per GPU")
     ap.add_argument("--per-request", type=int, default=128, help="samples per train request")
     ap.add_argument("--batches-per-step", type=int, default=0,
@@ -1352,6 +1477,7 @@ def main() -> None:
             dist.barrier()
 
     mix_log = []          # per-MIX stats (bytes per rank, begin->done latency) of the timed steps
+    step_samples = []     # what the train calls of the current step returned (--dump-outputs)
 
     def finish_mix():
         if pending[0] is not None:
@@ -1391,6 +1517,7 @@ def main() -> None:
         lens = np.asarray(arena.lens, np.int64)
         n = clf.train_arena(arena, offs, lens)
         assert n == samples_per_batch
+        step_samples.append(n)
         if world > 1 and mix_due():
             mixes[0] += 1
             if args.mix_mode == "sync":
@@ -1430,6 +1557,7 @@ def main() -> None:
     mix_log.clear()
     t0 = time.perf_counter()
     for i in range(args.steps):
+        step_samples.clear()
         for j in range(bps):
             train_batch(fresh.batches[i * bps + j])
         if trace_steps:
@@ -1458,35 +1586,48 @@ def main() -> None:
     updated = st1["updated"] - st0["updated"]
     replayed = clf._scan_stats.get("replayed", 0)
 
-    # accuracy on a held-out synthetic request (sanity: the model learns)
-    test = make_requests(random.Random(99), 1, 2048, args.labels, args.str_features,
-                         args.num_features, args.vocab)[0]
-    items = msgpack.unpackb(test, raw=False)
-    res = clf.classify_requests([msgpack.packb([d for _, d in items], use_bin_type=False)])
-    acc = float(np.mean([max(r, key=lambda t: t[1])[0] == lab for r, (lab, _) in zip(res, items)]))
+    # everything below the timed steps is a secondary record (--full) or the
+    # output dump: a plain run goes straight to the result line
+    full = args.full
+    acc = p50 = p99 = None
+    dump = args.dump_outputs if rank == 0 else None
+    # the model is the same in every run where the update order is defined
+    ordered = world == 1 and (device is None or args.update_mode == "exact")
+    last_batch = _last_scan_batch(clf) if dump else {}
+    if full or dump:
+        # a held-out synthetic request (sanity: the model learns)
+        items, body = _heldout_request(args)
+    if full or (dump and ordered):
+        res = clf.classify_requests([body])
+    if dump:
+        model = _model_arrays(clf, updated, [[v for _, v in r] for r in res]) if ordered else \
+            serial_probe(args, cfg, device, fresh.batches[args.steps * bps - 1], body)
+        dump_outputs(dump, clf, [bps, args.steps], step_samples, last_batch, trained, model)
+    if full:
+        acc = float(np.mean([max(r, key=lambda t: t[1])[0] == lab for r, (lab, _) in zip(res, items)]))
 
-    # classify latency: one datum per request, full round trip incl. D2H
-    one = msgpack.packb([items[0][1]], use_bin_type=False)
-    lat = []
-    for i in range(args.latency_iters + 20):
-        t1 = time.perf_counter()
-        clf.classify_requests([one])
-        dt = time.perf_counter() - t1
-        if i >= 20:
-            lat.append(dt * 1e6)
-    lat.sort()
-    p50 = statistics.median(lat)
-    p99 = lat[min(len(lat) - 1, int(0.99 * len(lat)))]
+        # classify latency: one datum per request, full round trip incl. D2H
+        one = msgpack.packb([items[0][1]], use_bin_type=False)
+        lat = []
+        for i in range(args.latency_iters + 20):
+            t1 = time.perf_counter()
+            clf.classify_requests([one])
+            dt = time.perf_counter() - t1
+            if i >= 20:
+                lat.append(dt * 1e6)
+        lat.sort()
+        p50 = round(statistics.median(lat), 1)
+        p99 = round(lat[min(len(lat) - 1, int(0.99 * len(lat)))], 1)
 
     exact = None
-    if world == 1 and device is not None and args.exact_steps > 0 and args.update_mode != "exact":
+    if full and world == 1 and device is not None and args.exact_steps > 0 and args.update_mode != "exact":
         exact = exact_record(args, cfg, device, warm, fresh, bps, samples_per_batch, sync)
     bf16 = None
-    if world == 1 and device is not None and args.bf16_steps > 0 and args.weight_dtype == "fp32":
+    if full and world == 1 and device is not None and args.bf16_steps > 0 and args.weight_dtype == "fp32":
         bf16 = exact_record(args, cfg, device, warm, fresh, bps, samples_per_batch, sync,
                             mode=args.update_mode, weight_dtype="bf16", steps=args.bf16_steps)
     worst = None
-    if world == 1 and device is not None and args.worst_steps > 0 and not args.worst_case:
+    if full and world == 1 and device is not None and args.worst_steps > 0 and not args.worst_case:
         # the headline's update mode on the worst-case stream: string values
         # are fresh noise, so (almost) every sample updates the model
         wb = 16
@@ -1525,7 +1666,7 @@ def main() -> None:
                 exact["worst_case"]["value"] / max(1.0, exact["cpu_baseline"]["worst_case_threads_1"]["value"]), 2)
         del ws
     served = served_native = None
-    if world == 1 and device is not None and not args.no_rpc:
+    if full and world == 1 and device is not None and not args.no_rpc:
         served = served_train(args, local, nat)
         served_native = served_train_native(args, local, nat)
         if isinstance(served_native, dict) and "error" not in served_native:
@@ -1537,10 +1678,10 @@ def main() -> None:
             served_native["learning_stream_exact"] = served_train_native(args, local, nat, mode="exact",
                                                                          noise_pm=20, classify=False)
     engines = None
-    if world == 1 and device is not None and args.engines != "none":
+    if full and world == 1 and device is not None and args.engines != "none":
         engines = engine_records(args, local)
     engines_dist = None
-    if world > 1 and args.dist_engines != "none":
+    if full and world > 1 and args.dist_engines != "none":
         if args.dist_engine_rows <= 0:
             args.dist_engine_rows = 100_000 if device is not None else 300
         if args.dist_cluster_points <= 0:
@@ -1615,9 +1756,10 @@ def main() -> None:
             "served_native": served_native,
             "engines": engines,
             "engines_dist": engines_dist,
-            "classify_latency_us_p50": round(p50, 1),
-            "classify_latency_us_p99": round(p99, 1),
-            "heldout_accuracy": round(acc, 4),
+            "full": full,
+            "classify_latency_us_p50": p50,
+            "classify_latency_us_p99": p99,
+            "heldout_accuracy": round(acc, 4) if acc is not None else None,
             "baseline_note": "reference publishes no numbers (BASELINE.md)",
         }
         # the key records again, last: the driver keeps the tail of the line

@@ -298,6 +298,7 @@ class FeaturePipeline:
         self._gsets: list[_ScanSet] | None = None     # created on the first GPU-scan batch
         self._gnext = 0
         self._gprev = None
+        self._glast = None              # (set, R, n, slot_cap) of the last batch, if the GPU scan took it
         self.set_wait_s = 0.0           # host time waiting for a device set to come free
 
         self._ltab = None                 # (label version, device hash, meta, blob)
@@ -351,6 +352,7 @@ class FeaturePipeline:
         the arena prefix to HBM."""
         if not (self.fast or self.wide):
             raise RuntimeError("converter config is not eligible for the GPU path")
+        self._glast = None             # this batch goes through the host scanner
         nat = native()
         pin = self._pinned[self._turn]
         self._turn ^= 1
@@ -421,6 +423,7 @@ class FeaturePipeline:
         self._gnext = (turn + 1) % len(self._gsets)
         self._gprev = turn
         st = self._gsets[turn]
+        self._glast = (st, R, n, slot_cap)
         if st.used:
             t0 = time.perf_counter()
             st.free.synchronize()          # its last batch's train (and so its copies) finished
@@ -504,6 +507,18 @@ class FeaturePipeline:
         hip.train_batch_submit(a)
         R, n, t = int(a.R), int(a.n), st.bufs.t
         return DeviceBatch(n, int(a.slot_cap), R, t["row_ptr"], t["fidx"], t["fval"], t["labels"],
+                           t["scan_meta"][2 * R:3 * R + 1], ready=st.ready)
+
+    def last_scan_batch(self) -> DeviceBatch | None:
+        """The device CSR the GPU scan and fv_hash made of the last arena
+        batch (valid once the batch's work has completed, until its set is
+        reused four batches later). None: no batch yet, or the last one went
+        through the host scanner (from_arena)."""
+        if self._glast is None:
+            return None
+        st, R, n, slot_cap = self._glast
+        t = st.bufs.t
+        return DeviceBatch(n, slot_cap, R, t["row_ptr"], t["fidx"], t["fval"], t["labels"],
                            t["scan_meta"][2 * R:3 * R + 1], ready=st.ready)
 
     def _launch(self, pin: "_Pinned", src: torch.Tensor, n: int, nbytes: int, nslots: int,

@@ -74,7 +74,7 @@ def test_bench_eight_ranks_cpu():
     rank is bounded by --fresh-gb (here a few MB per rank)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(WORLD), "--steps", "2",
-           "--warmup", "1", "--device", "cpu", "--requests", "4", "--per-request", "8",
+           "--warmup", "1", "--full", "--device", "cpu", "--requests", "4", "--per-request", "8",
            "--hash-bits", "10", "--latency-iters", "2", "--batches-per-step", "2", "--engines", "none",
            "--dist-engines", "lof,kmeans,arow", "--dist-engine-rows", "120", "--dist-engine-seconds", "0.5",
            "--dist-cluster-points", "3000", "--dist-train-seconds", "1.5"]

@@ -26,7 +26,7 @@ def _port():
 def test_two_ranks_one_gpu_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "4", "--warmup", "2", "--dist-backend", "gloo",
+           "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--dist-backend", "gloo",
            "--requests", "64", "--per-request", "32", "--hash-bits", "16", "--latency-iters", "5",
            "--batches-per-step", "3",
            # the distributed engine records at a rehearsal size (the BASELINE-scale

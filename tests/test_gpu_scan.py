@@ -102,6 +102,40 @@ def test_gpu_scan_matches_host_scan(nlabels):
     np.testing.assert_array_equal(chk.hist[:128], want)
 
 
+def test_last_scan_batch_is_the_trained_batch():
+    """FeaturePipeline.last_scan_batch after LinearClassifier.train_arena:
+    the device CSR of the batch the GPU scan just took equals the host
+    scanner's; None before any batch and after a batch that went through
+    the host scanner"""
+    import torch
+    from jubatus_amd.models.classifier import LinearClassifier
+
+    clf = LinearClassifier("AROW", {"regularization_weight": 1.0}, DatumToFvConverter(CONV), device=_device(),
+                           concurrent_update="atomic")
+    for y in range(5):
+        clf.set_label(f"L{y}")
+    assert clf.pipe.last_scan_batch() is None
+    rng = random.Random(3)
+
+    def bodies(nreq):          # requests the device scan stages (well below its LDS window)
+        return [msgpack.packb([[f"L{rng.randrange(5)}", _sample(rng, rng.randrange(5))]
+                               for _ in range(rng.randrange(1, 40))], use_bin_type=False) for _ in range(nreq)]
+    first = _arena(bodies(12))
+    arena, offs, lens = _arena(bodies(33))
+    for a, o, l in (first, (arena, offs, lens)):         # the second batch is the last one
+        clf.train_arena(a, o, l)
+    clf.synchronize()
+    assert clf._scan_stats["gpu"] == 2 and clf._scan_stats["replayed"] == 0
+    dev = _batch_arrays(clf.pipe.last_scan_batch())
+    host = _batch_arrays(clf.pipe.from_arena(arena, offs, lens, True, clf.labels))
+    torch.cuda.synchronize()
+    clf.pipe.check_errors()
+    assert dev[0] == host[0] > 0
+    for h, d, name in zip(host[1:], dev[1:], ("row_ptr", "labels", "stream_ptr", "fidx", "fval")):
+        np.testing.assert_array_equal(h, d, err_msg=name)
+    assert clf.pipe.last_scan_batch() is None            # from_arena: the host scanner took the last batch
+
+
 @pytest.mark.parametrize("case", ["unknown_label", "binary_values", "malformed", "too_big"])
 def test_gpu_scan_rejects_batch(case):
     import torch

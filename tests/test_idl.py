@@ -3,6 +3,8 @@ reference's service IDLs (jubatus/server/server/*.idl - every method's
 argument / return types, routing, request type, aggregator and every message
 layout)."""
 import glob
+import hashlib
+import json
 import os
 import types
 
@@ -24,10 +26,45 @@ def test_specs_idl_roundtrip(engine):
         assert f.read() == text
 
 
+def _digest(*parts) -> str:
+    return hashlib.sha256("\x1f".join(str(p) for p in parts).encode()).hexdigest()[:20]
+
+
+def idl_digests(f) -> dict:
+    """one digest per message layout and per method of a parsed IDL file,
+    over exactly what jenerator.check compares: message name and its
+    "type name" fields; method name, argument types, return type, routing
+    (with the owner count of cht), request type and aggregator"""
+    return {"messages": sorted(_digest("message", m.name, *[f"{jdl.norm_type(fl.type)} {fl.name}" for fl in m.fields])
+                               for m in f.messages),
+            "methods": sorted(_digest("method", m.name, ",".join(jdl.norm_type(a.type) for a in m.args),
+                                      jdl.norm_type(m.ret), m.routing, m.cht_n if m.routing == "cht" else 0,
+                                      m.lock, m.agg)
+                              for s in f.services for m in s.methods)}
+
+
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_idl_digests.json")) as _f:
+    REFERENCE_DIGESTS = json.load(_f)
+
+
 @pytest.mark.skipif(not os.path.isdir(REF_IDL), reason="reference tree not present")
 @pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(REF_IDL, "*.idl"))))
 def test_reference_idl_parity(path):
     assert jenerator.check(jdl.parse_file(path)) == []
+
+
+@pytest.mark.parametrize("engine", sorted(specs.SERVICES))
+def test_reference_idl_digests(engine):
+    """the same parity where no reference tree is at hand:
+    tests/golden/reference_idl_digests.json holds idl_digests() of the
+    reference's <engine>.idl (recorded once from its tree: digests only, no
+    IDL text). The specs must define every message the reference's file
+    defines with the same layout, and exactly its methods with the same
+    types, routing, request type and aggregator."""
+    ref = REFERENCE_DIGESTS[engine]
+    mine = idl_digests(jenerator.service_from_specs(engine))
+    assert ref["methods"] and ref["methods"] == mine["methods"]
+    assert set(ref["messages"]) <= set(mine["messages"])
 
 
 def test_parser_features_and_errors():

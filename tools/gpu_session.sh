@@ -41,11 +41,11 @@ for s in $STEPS; do
     kbench) run kbench 300 python tools/bench_train_kernel.py ;;
     scan) run scan 300 python tools/bench_scan.py ;;
     engines) run engines 900 python tools/bench_engines.py ;;
-    bench) run bench 600 python bench.py --steps 20 --warmup 3 ;;
+    bench) run bench 600 python bench.py --steps 20 --warmup 3 --full ;;
     prof)
       rm -rf "$OUT/prof"
       (cd /tmp && run prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-         python "$ROOT/bench.py" --steps 5 --warmup 2 --latency-iters 20)
+         python "$ROOT/bench.py" --steps 5 --warmup 2 --full --latency-iters 20)
       find "$OUT/prof" -name "*stats*" | head -20 ;;
     lof)   # LOF engine record (native server over RPC) + its kernel stats
       run lof 300 python tools/bench_engine_records.py --engines anomaly_lof

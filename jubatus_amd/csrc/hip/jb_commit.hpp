@@ -1,8 +1,8 @@
-// Pieces shared by the serial-equivalent committers of label capacities up to
-// 64 (commit.hip: the delta committer; vcommit.hip: the verified committer):
-// the LDS row store (2-choice 4-way buckets of row keys), the exact margin of a
-// sample held by a 16-lane group, its slack to the method's update threshold,
-// and the round-start score correction over the store's delta rows.
+// Pieces of the verified committer (vcommit.hip: serial-equivalent training
+// at label capacities up to 64) that stand on their own: the LDS row store
+// (2-choice 4-way buckets of row keys), the exact margin of a sample held by a
+// 16-lane group, its slack to the method's update threshold, and the
+// round-start score correction over the store's delta rows.
 #pragma once
 #include <stdlib.h>
 
@@ -11,32 +11,8 @@
 namespace jb {
 namespace dc {
 
-constexpr int kT = 512;               // committer threads (8 waves)
-constexpr int kNG = kT / 16;          // groups (DPP rows) of 16 lanes
-constexpr int kR = 2;                 // samples per group per round
-constexpr int kNS = kNG * kR;         // samples per round
-constexpr int kFC = 2;                // feature chunks of 16 held in registers
-constexpr int kNFMax = 16 * kFC;      // widest sample the committer takes
 constexpr float kGuard = 1e-4f;       // relative guard band of a decision
 constexpr int kInf = 0x7fffffff;
-// stop reasons (tail[kTailReason]); the values are serial.hip's
-constexpr int64_t kStopDone = 0, kStopSaturated = 1, kStopDense = 2, kStopWindow = 3;
-constexpr int kTailReason = 20;
-// A segment scores and commits a window of the batch, not its whole rest:
-// twice the samples the previous segment took, at least kWinMin (the S0
-// pass of a segment that saturates early would otherwise re-score the whole
-// rest of the batch every time). tail[kTailWin]: samples the last segment took.
-constexpr int kTailWin = 29;
-constexpr int64_t kWinMin = 8192;
-__device__ __forceinline__ int64_t window_end(int64_t beg, int64_t end, const int64_t* tail) {
-  int64_t w = tail[kTailWin];   // the previous batch's last segment for a batch's first one
-  w = (w <= 0 || w > ((int64_t)1 << 30)) ? kWinMin : (2 * w > kWinMin ? 2 * w : kWinMin);
-  return beg + w < end ? beg + w : end;
-}
-// phase timing (tail[4..19]): shader cycles of wave 0 per phase, the wall
-// clock of the kernel and every wave's own round-start work
-// (a kernel argument: JB_COMMIT_PROF=1 turns them on; they cost ~6 % of a
-// steady batch, so the default run leaves them off)
 
 constexpr int ilog2(int v) { return v <= 1 ? 0 : 1 + ilog2(v / 2); }
 

@@ -6,6 +6,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "jb_serial_layout.hpp"
+
 namespace jb {
 namespace vc {
 
@@ -29,12 +31,7 @@ enum : int {
 enum : int { kWhyEnd = 0, kWhySat = 1, kWhyDense = 2 };
 // first stepper chunk after a dense window; chunks double up to kDenseChunkMax
 constexpr int64_t kDenseChunk0 = 8192, kDenseChunkMax = 1 << 20;
-// tail words (the batch's int64 x 32 diagnostics, jb_commit.hpp) the stepper
-// chunks report through
-constexpr int kTailStepped = 16, kTailChunks = 17, kTailSegEst = 18, kTailCsWindows = 19;
-// tail[kTailReasonW]: the batch's stop reason (jb_commit.hpp dc::kTailReason / kStop*)
-constexpr int kTailReasonW = 20;
-constexpr int64_t kReasonDone = 0, kReasonSaturated = 1;
+// (the batch's tail words and stop reasons: jb_serial_layout.hpp)
 
 // Candidates on the stepper (JB_VC_CS / JB_VC_CS_PM, see vcommit.hip): an
 // update-heavy window's candidates are walked by the sequential stepper instead of the

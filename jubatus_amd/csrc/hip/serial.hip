@@ -32,9 +32,14 @@
 // Rounding: the M0 margin and the exact rescoring sum in different orders, so
 // the slack keeps a relative guard band (kSlackGuard) - a sample within it of
 // the threshold always takes the exact step.
+//
+// These kernels (the bound committer) serve label capacities past 64. The
+// entry point jb_serial_prepare hands capacities up to 64 to the verified
+// committer (vcommit.hip) and sizes its segment budget.
 #include "jb_linear.hpp"
+#include "jb_serial_layout.hpp"
+#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <algorithm>
 #include <mutex>
 #include <unordered_map>
@@ -52,24 +57,22 @@ constexpr float kSlackGuard = 1e-4f; // relative guard band of the slack
 constexpr int kStepBits = 8;
 constexpr int kStepCap = 1 << kStepBits;  // step table slots
 constexpr int kStepList = 64;        // distinct rows of one step the table holds
-// why a committer stopped (tail[kTailReason]): the batch is done, the D
-// table saturated (a new segment re-scores the rest against the current
-// model with an empty table), or too many updates per round (the rest goes
-// to the sequential kernel)
-constexpr int kTailReason = 20;
+// Why the committer stopped (tail[kTailReason], jb_serial_layout.hpp): the
+// batch is done, the D table saturated (a new segment re-scores the rest
+// against the current model with an empty table), or too many updates per
+// round (the rest goes to the sequential kernel).
 // kStopRescore: the segment's exact steps that did not update passed
 // rescore_waste - the bound, grown by every step since the segment's scores,
 // no longer settles samples that would not update; scoring the rest of the
 // batch again against the live model (whole GPU, ~tens of us) is cheaper than
 // more wasted single-wave steps (~3.4 us each, profiles/r03_serial_v5_segments.jsonl)
-constexpr int64_t kStopDone = 0, kStopSaturated = 1, kStopDense = 2, kStopRescore = 3;
-constexpr int kSerialSegments = 4;       // segments of a small batch
+constexpr int kSerialSegments = 4;       // bound committer: segments of a small batch
 constexpr int kSerialSegmentsBig = 48;   // of a batch of >= kSerialBigBatch samples
 constexpr int64_t kSerialBigBatch = 16384;
-constexpr int kDeltaSegmentsMin = 8;     // delta committer segments of a big batch
-constexpr int kDeltaSegmentsMax = 512;
-// verified committer windows of a big batch (vcommit.hip); a segment costs
-// ~20 us, a sequential tail ~2 us per sample
+// verified committer (vcommit.hip): windows of a small batch and the least a
+// big one gets, and the most; a segment costs ~20 us, a sequential tail ~2 us
+// per sample
+constexpr int kVerifiedSegmentsMin = 8;
 constexpr int kVerifiedSegmentsMax = 2048;
 constexpr int kRescoreWaste = 16;        // wasted exact steps that end a segment
 constexpr int kScoreMaxBlocks = 8192;    // serial_score_kernel grid cap (grid-stride)
@@ -542,9 +545,9 @@ __device__ __forceinline__ void load_features(int32_t (&fi)[NF], float (&fx)[NF]
 // owns sample p + t of the round starting at p, with the sample's slack,
 // label and features in registers (prefetched a round ahead: one load round
 // trip per round). The owner of the first unsettled sample stages it in LDS
-// for wave 0's exact step. tail[0] receives the first sample it did not
-// settle (the end of the batch when it finished), tail[1] the end of the
-// batch: the exact single-stream kernel runs [tail[0], tail[1]).
+// for wave 0's exact step. tail[kTailStart] receives the first sample it did
+// not settle (the end of the batch when it finished), tail[kTailEnd] the end
+// of the batch: the exact single-stream kernel runs that range.
 template <int LC>
 __global__ __launch_bounds__(kCommitThreads) void serial_commit_kernel(
     const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ fidx,
@@ -754,17 +757,18 @@ __global__ __launch_bounds__(kCommitThreads) void serial_commit_kernel(
   __syncthreads();
   // diagnostics of the batch: the first segment sets them, later ones add
   auto put = [&](int i, int64_t v) { tail[i] = seg == 0 ? v : tail[i] + v; };
-  if (lane == 0) put(12 + wv, (int64_t)wwork);
+  if (lane == 0) put(kTailBoundWave0 + wv, (int64_t)wwork);
   if (tid == 0) {
-    tail[0] = stop;
-    tail[1] = end;
+    tail[kTailStart] = stop;
+    tail[kTailEnd] = end;
     tail[kTailReason] = why;
-    put(2, n_steps);        // exact steps, rounds
-    put(3, n_rounds);
-    put(21, 1);             // segments
-    for (int i = 0; i < 6; ++i) put(4 + i, (int64_t)ph[i]);
-    put(10, kSerialTiming ? (int64_t)(wall_clock64() - w0) : 0);    // 100 MHz ticks
-    put(11, (int64_t)(stamp() - tc) + (int64_t)(ph[0] + ph[1] + ph[2] + ph[3] + ph[4] + ph[5]));
+    put(kTailSteps, n_steps);
+    put(kTailRounds, n_rounds);
+    put(kTailSegments, 1);
+    for (int i = 0; i < 6; ++i) put(kTailBoundPhase0 + i, (int64_t)ph[i]);
+    put(kTailBoundWall, kSerialTiming ? (int64_t)(wall_clock64() - w0) : 0);    // 100 MHz ticks
+    put(kTailBoundCycles,
+        (int64_t)(stamp() - tc) + (int64_t)(ph[0] + ph[1] + ph[2] + ph[3] + ph[4] + ph[5]));
     if (stats != nullptr && s_valid > 0) atomicAdd(stats + 1, (unsigned long long)s_valid);
   }
   if (tid == 0 && stats != nullptr && n_upd > 0) atomicAdd(stats, (unsigned long long)n_upd);
@@ -772,63 +776,49 @@ __global__ __launch_bounds__(kCommitThreads) void serial_commit_kernel(
 
 }  // namespace jb
 
-// commit.hip: per-sample scratch bytes of the delta committer
-extern "C" int64_t jb_delta_scratch_per_sample();
-
-// bytes of the kSerial scratch for batches of up to n_max samples:
-// [tail int64 x 32 = 256 B][per sample: the delta committer's S0 scores,
-// precisions and best wrong label (commit.hip, LC <= 64) or this file's
-// slack + |x|_1 (LC > 64)]; n_max bounds the batch's sample count
+// bytes of the kSerial scratch for batches of up to n_max samples at any
+// label capacity (the verified committer's, the larger of the two layouts of
+// jb_serial_layout.hpp); n_max bounds the batch's sample count
 // stream_ptr[nstreams] - stream_ptr[0]
-extern "C" int64_t jb_vcommit_fixed_bytes();
 extern "C" int64_t jb_serial_scratch_bytes(int64_t n_max) {
-  const int64_t n = n_max > 0 ? n_max : 1;
-  // vcommit.hip: the slack of every sample (4 B) after the records, then its
-  // 256-aligned fixed region (state, candidate bits, staged store)
-  return 256 + ((jb_delta_scratch_per_sample() + 4) * n + 255) / 256 * 256 + jb_vcommit_fixed_bytes();
+  return jb::VcScratch::bytes(n_max > 0 ? n_max : 1);
 }
 
 // the scratch a label capacity needs: past 64 labels only the bound
-// committer runs (tail words, slack and |x|_1 per sample: 8 B a sample)
+// committer runs
 extern "C" int64_t jb_serial_scratch_bytes_lc(int64_t n_max, int LC) {
-  const int64_t n = n_max > 0 ? n_max : 1;
-  if (LC > 64) return 256 + (8 * n + 255) / 256 * 256;
-  return jb_serial_scratch_bytes(n_max);
+  return LC > 64 ? jb::BoundScratch::bytes(n_max > 0 ? n_max : 1) : jb_serial_scratch_bytes(n_max);
 }
 
-// commit.hip: the delta committer (label capacities <= 64)
-extern "C" int jb_delta_prepare(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
-                                const int32_t* labels, const int64_t* stream_ptr, int nstreams,
-                                int64_t n_max, float* W, float* S, const int32_t* active, int LC,
-                                int method, float C, unsigned long long* stats, uint8_t* touched,
-                                void* scratch, int nseg, hipStream_t stream);
-
-// pinned host words per scratch buffer: the last delta batch's final stop
-// reason and segment count (tail[20], tail[21])
-static std::mutex& delta_seen_mu() {
+// pinned host words per scratch buffer, read back after every batch of the
+// verified committer: its final stop reason, the segments it used and the
+// segments it would have used without stepper chunks
+enum : int { kSeenReason = 0, kSeenSegments, kSeenSegEst, kSeenWords };
+static_assert(jb::kTailSegments == jb::kTailReason + 1, "one copy reads back both");
+static std::mutex& seen_mu() {
   static std::mutex mu;
   return mu;
 }
-static std::unordered_map<void*, int64_t*>& delta_seen_map() {
+static std::unordered_map<void*, int64_t*>& seen_map() {
   static std::unordered_map<void*, int64_t*> seen;
   return seen;
 }
-static int64_t* delta_segments_seen(void* scratch) {
-  std::lock_guard<std::mutex> g(delta_seen_mu());
-  auto& seen = delta_seen_map();
+static int64_t* segments_seen(void* scratch) {
+  std::lock_guard<std::mutex> g(seen_mu());
+  auto& seen = seen_map();
   auto it = seen.find(scratch);
   if (it != seen.end()) return it->second;
   int64_t* p = nullptr;
-  if (hipHostMalloc((void**)&p, 4 * sizeof(int64_t), hipHostMallocDefault) != hipSuccess) return nullptr;
+  if (hipHostMalloc((void**)&p, kSeenWords * sizeof(int64_t), hipHostMallocDefault) != hipSuccess) return nullptr;
   // until the first batch reports: done in 128 segments (a host running
   // batches ahead of the device must not read "unknown" as "short": every
-  // batch would get all 512 and pay ~12 us per empty one; a young model's
-  // first batches need ~100-300, so 2 x 128 + 4 keeps them whole - with 2 x
-  // 64 + 4 the first ones handed a sequential tail on: 86 vs 45 ms for
-  // batches 0-5, profiles/serial_exact_r4_prof_switch.jsonl)
-  p[0] = jb::kStopDone;
-  p[1] = 128;
-  p[2] = 0;   // (verified committer) segment estimate with its stepper chunks
+  // batch would get every segment and pay for the empty ones; a young
+  // model's first batches need ~100-300, and with 64 here the first ones
+  // handed a sequential tail on: 86 vs 45 ms for batches 0-5,
+  // profiles/serial_exact_r4_prof_switch.jsonl)
+  p[kSeenReason] = jb::kStopDone;
+  p[kSeenSegments] = 128;
+  p[kSeenSegEst] = 0;
   seen[scratch] = p;
   return p;
 }
@@ -843,8 +833,8 @@ extern "C" int jb_vcommit_prepare(const int64_t* row_ptr, const int32_t* fidx, c
 // a scratch buffer's owner (re)allocated it: the pinned words of a freed
 // buffer that had the same address must not carry its segment history over
 extern "C" int jb_serial_scratch_forget(void* scratch) {
-  std::lock_guard<std::mutex> g(delta_seen_mu());
-  auto& seen = delta_seen_map();
+  std::lock_guard<std::mutex> g(seen_mu());
+  auto& seen = seen_map();
   auto it = seen.find(scratch);
   if (it == seen.end()) return 0;
   (void)hipHostFree(it->second);
@@ -852,23 +842,33 @@ extern "C" int jb_serial_scratch_forget(void* scratch) {
   return 1;
 }
 
-// committer of LC <= 64: 2 = verified (vcommit.hip, default), 1 = delta
-// (commit.hip, JB_SERIAL_COMMITTER=delta), 0 = this file's bound committer
-// (JB_SERIAL_COMMITTER=bound); the last two for A/B runs
-static int serial_committer() {
-  static const int v = [] {
-    const char* e = getenv("JB_SERIAL_COMMITTER");
-    if (e != nullptr && strcmp(e, "bound") == 0) return 0;
-    if (e != nullptr && strcmp(e, "delta") == 0) return 1;
-    return 2;
+// Segments (windows) a batch of the verified committer gets, from what the
+// previous batch on the same scratch reported: prev segments used, est the
+// segments its stepper chunks stood in for as well (vcommit.hip seg_estimate:
+// a batch that is sparse again after a dense one must not run out), why its
+// stop reason. A batch that runs out of segments hands its rest to the
+// sequential kernel, so the batch after one that ran short gets them all.
+static int segment_budget(int64_t n_max, int64_t prev, int64_t est, int64_t why) {
+  if (n_max < jb::kSerialBigBatch) return jb::kVerifiedSegmentsMin;
+  if (why != jb::kStopDone && why != jb::kStopDense) return jb::kVerifiedSegmentsMax;
+  // slack over the previous batch's count: prev / 2 + 8 by default
+  // (JB_VC_SEG_SLACK = d,c: prev / d + c, an A/B knob)
+  static const std::pair<int, int> slack = [] {
+    const char* e = getenv("JB_VC_SEG_SLACK");
+    int d = 2, c = 8;
+    if (e != nullptr && sscanf(e, "%d,%d", &d, &c) != 2) { d = 2; c = 8; }
+    return std::make_pair(d > 0 ? d : 2, c >= 0 ? c : 8);
   }();
-  return v;
+  prev = std::max(prev, est);
+  return (int)std::min<int64_t>(jb::kVerifiedSegmentsMax,
+                                std::max<int64_t>(jb::kVerifiedSegmentsMin,
+                                                  prev + prev / slack.first + slack.second));
 }
 
 // Steps 1-2 of a kSerial batch (score, commit); the caller then runs the
 // exact single-stream kernel over stream_ptr = (int64_t*)scratch (step 3).
-// bail_after: exact steps per 1024-sample round past which the committer
-// hands the rest of the batch to the sequential kernel.
+// bail_after: exact steps per round past which the bound committer hands the
+// rest of the batch to the sequential kernel.
 extern "C" int jb_serial_prepare(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
                                  const int32_t* labels, const int64_t* stream_ptr, int nstreams,
                                  int64_t n_max, float* W, float* S, const int32_t* active, int LC,
@@ -878,81 +878,40 @@ extern "C" int jb_serial_prepare(const int64_t* row_ptr, const int32_t* fidx, co
   if (nstreams <= 0 || n_max <= 0) return 0;
   if (scratch == nullptr || scratch_bytes < jb_serial_scratch_bytes_lc(n_max, LC)) return -3;
   if (method >= jb::CW && S == nullptr) return -4;
-  if (LC <= 64 && serial_committer() == 2) {
+  int64_t* tail = (int64_t*)scratch;
+  if (LC <= 64) {
     // verified committer: a segment is one window (score, gather, commit,
     // verify); a window that fails verification runs again. The count follows
-    // the segments the previous batch on this scratch used (pinned readback,
-    // one batch late at worst); the rest of a batch that runs out of them goes
-    // to the sequential kernel.
-    int nseg = jb::kSerialSegments;
-    int64_t* seen = delta_segments_seen(scratch);
-    if (n_max >= jb::kSerialBigBatch) {
-      const int64_t why = seen != nullptr ? ((volatile int64_t*)seen)[0] : 0;
-      // (with the windows the previous batch's stepper chunks stood in for -
-      // vcommit.hip seg_estimate: a batch that is sparse again after a dense
-      // one must not run out of segments)
-      const int64_t est = seen != nullptr ? ((volatile int64_t*)seen)[2] : 0;
-      const int64_t prev = std::max<int64_t>(seen != nullptr ? ((volatile int64_t*)seen)[1] : 0, est);
-      const bool short_of = why != jb::kStopDone && why != jb::kStopDense;
-      // slack over the previous batch's count: prev / 2 + 8 by default
-      // (JB_VC_SEG_SLACK = d,c: prev / d + c, an A/B knob)
-      static const std::pair<int, int> slack = [] {
-        const char* e = getenv("JB_VC_SEG_SLACK");
-        int d = 2, c = 8;
-        if (e != nullptr && sscanf(e, "%d,%d", &d, &c) != 2) { d = 2; c = 8; }
-        return std::make_pair(d > 0 ? d : 2, c >= 0 ? c : 8);
-      }();
-      nseg = short_of ? jb::kVerifiedSegmentsMax
-                      : (int)std::min<int64_t>(jb::kVerifiedSegmentsMax,
-                                               std::max<int64_t>(jb::kDeltaSegmentsMin,
-                                                                 prev + prev / slack.first + slack.second));
-    } else {
-      nseg = 8;
-    }
+    // the previous batch on this scratch (pinned readback, one batch late at
+    // worst).
+    volatile int64_t* seen = segments_seen(scratch);
+    const int nseg = seen != nullptr
+                         ? segment_budget(n_max, seen[kSeenSegments], seen[kSeenSegEst], seen[kSeenReason])
+                         : segment_budget(n_max, 0, 0, jb::kStopDone);
     const int rc = jb_vcommit_prepare(row_ptr, fidx, fval, labels, stream_ptr, nstreams, n_max, W, S, active,
                                       LC, method, C, stats, touched, scratch, nseg, stream);
     if (rc == 0 && seen != nullptr) {
-      (void)hipMemcpyAsync(seen, (int64_t*)scratch + 20, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, stream);
-      (void)hipMemcpyAsync(seen + 2, (int64_t*)scratch + 18, sizeof(int64_t), hipMemcpyDeviceToHost, stream);
+      int64_t* host = const_cast<int64_t*>(seen);
+      (void)hipMemcpyAsync(host + kSeenReason, tail + jb::kTailReason, 2 * sizeof(int64_t), hipMemcpyDeviceToHost,
+                           stream);
+      (void)hipMemcpyAsync(host + kSeenSegEst, tail + jb::kTailSegEst, sizeof(int64_t), hipMemcpyDeviceToHost,
+                           stream);
     }
     return rc;
   }
-  if (LC <= 64 && serial_committer() == 1) {
-    // delta committer: segments end only when the LDS row store fills. A
-    // segment that finds the batch done costs two empty launches (~4 us), a
-    // batch that runs out of segments hands its rest to the sequential kernel:
-    // the count follows the segments the previous batch on this scratch used
-    // (read back asynchronously into pinned memory, one batch late at worst)
-    // A batch after one that ran out of segments (its last stop reason is
-    // not done / dense: the rest went to the sequential kernel, ~100x slower
-    // per sample) gets every segment.
-    int nseg = jb::kSerialSegments;
-    int64_t* seen = delta_segments_seen(scratch);
-    if (n_max >= jb::kSerialBigBatch) {
-      const int64_t why = seen != nullptr ? ((volatile int64_t*)seen)[0] : 0;
-      const int64_t prev = seen != nullptr ? ((volatile int64_t*)seen)[1] : 0;
-      const bool short_of = why != jb::kStopDone && why != jb::kStopDense;
-      nseg = short_of ? jb::kDeltaSegmentsMax
-                      : (int)std::min<int64_t>(jb::kDeltaSegmentsMax,
-                                               std::max<int64_t>(jb::kDeltaSegmentsMin, 2 * prev + 4));
-    }
-    const int rc = jb_delta_prepare(row_ptr, fidx, fval, labels, stream_ptr, nstreams, n_max, W, S, active,
-                                    LC, method, C, stats, touched, scratch, nseg, stream);
-    if (rc == 0 && seen != nullptr)
-      (void)hipMemcpyAsync(seen, (int64_t*)scratch + 20, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, stream);
-    return rc;
-  }
-  int64_t* tail = (int64_t*)scratch;
-  float* slack = (float*)((uint8_t*)scratch + 256);
-  float* l1n = slack + n_max;     // |x|_1 of each sample
+  // bound committer (this file's kernels)
+  float* slack = (float*)((uint8_t*)scratch + jb::BoundScratch::slack_offset());
+  float* l1n = (float*)((uint8_t*)scratch + jb::BoundScratch::l1_offset(n_max));   // |x|_1 of each sample
   // (slack[i] belongs to sample stream_ptr[0] + i)
   const int64_t blocks = std::min<int64_t>((n_max * 64 + 255) / 256, jb::kScoreMaxBlocks);
   // a big batch that updates often re-scores its rest many times (kStopRescore);
   // the last segment never stops for that (its rest would go sequential)
   const int nseg = n_max >= jb::kSerialBigBatch ? jb::kSerialSegmentsBig : jb::kSerialSegments;
-  // segments: a committer that saturated its D table hands [tail[0], end)
-  // to the next segment (score + commit against the model as it is then);
-  // the range lives in tail[0..1] on the device, so no host round trip
+  // segments: a committer that saturated its D table hands [tail[kTailStart],
+  // end) to the next segment (score + commit against the model as it is
+  // then); the range lives in the first two tail words on the device, so no
+  // host round trip
+  static_assert(jb::kTailStart == 0 && jb::kTailEnd == 1, "the tail doubles as a one-stream stream_ptr");
   for (int seg = 0; seg < nseg; ++seg) {
     const int waste = seg + 1 < nseg ? jb::kRescoreWaste : 0;
     const int64_t* sp = seg == 0 ? stream_ptr : tail;
@@ -963,9 +922,15 @@ extern "C" int jb_serial_prepare(const int64_t* row_ptr, const int32_t* fidx, co
                      row_ptr, fidx, fval, labels, sp, ns, W, active, method, C, slack, l1n, why); \
   hipLaunchKernelGGL((jb::serial_commit_kernel<L>), dim3(1), dim3(jb::kCommitThreads), 0, stream, \
                      row_ptr, fidx, fval, labels, sp, ns, W, S, active, method, C, slack, l1n,    \
-                     stats,                                                                       \
-                     touched, tail, bail_after, seg, waste);
-    JB_LC_DISPATCH(LC, JB_SERIAL)
+                     stats, touched, tail, bail_after, seg, waste);                               \
+  break;
+    switch (LC) {   // the label capacities past the verified committer's
+      case 128: JB_SERIAL(128)
+      case 256: JB_SERIAL(256)
+      case 512: JB_SERIAL(512)
+      case 1024: JB_SERIAL(1024)
+      default: return -1;
+    }
 #undef JB_SERIAL
   }
   return (int)hipGetLastError();

@@ -1142,12 +1142,12 @@ __global__ __launch_bounds__(kT) void stepper_kernel(const int64_t* __restrict__
     vst[vc::S_STEPPED] += end - beg;
     vst[vc::S_NCHUNK] += 1;
     vst[vc::S_DCHUNK] = min(2 * vst[vc::S_DCHUNK], vc::kDenseChunkMax);
-    vtail[0] = done ? bend : end;
-    vtail[1] = bend;
-    vtail[vc::kTailReasonW] = done ? vc::kReasonDone : vc::kReasonSaturated;
-    vtail[vc::kTailStepped] = vst[vc::S_STEPPED];
-    vtail[vc::kTailChunks] = vst[vc::S_NCHUNK];
-    vtail[vc::kTailSegEst] = vc::seg_estimate(vst);
+    vtail[kTailStart] = done ? bend : end;
+    vtail[kTailEnd] = bend;
+    vtail[kTailReason] = done ? kStopDone : kStopSaturated;
+    vtail[kTailStepped] = vst[vc::S_STEPPED];
+    vtail[kTailChunks] = vst[vc::S_NCHUNK];
+    vtail[kTailSegEst] = vc::seg_estimate(vst);
   }
   if (PROF && prof != nullptr && lane == 0) {
 #pragma unroll

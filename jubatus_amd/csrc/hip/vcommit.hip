@@ -4,10 +4,10 @@
 // request order, as the reference's classifier does
 // (jubatus/server/server/classifier_serv.cpp:138-144).
 //
-// Why a new committer (round 5). The delta committer (commit.hip) walks every
-// sample of a batch through one 512-thread workgroup, 64 samples per round and
-// a workgroup barrier per round and per step, although ~98 % of the samples
-// never come near their update threshold. The host study of the bench stream
+// Why this shape. Its predecessor (the delta committer, since removed) walked
+// every sample of a batch through one 512-thread workgroup, 64 samples per
+// round and a workgroup barrier per round and per step, although ~98 % of the
+// samples never come near their update threshold. The host study of the bench stream
 // (tools/exact_study.py over jb_cpu_serial.cpp) shows that a sample's slack at
 // the segment start almost always exceeds the bound on what the segment's
 // updates can move its margin: with T = 0.5, ~6 % of a window are candidates
@@ -29,7 +29,7 @@
 //                       a step's increments go to the store, and every later
 //                       candidate of the round gets the step's correction from
 //                       the stamped rows. Candidate scores stay lazy under the
-//                       bounded slack (2 sum_f |x_f| rmax_f), as in commit.hip.
+//                       bounded slack (2 sum_f |x_f| rmax_f).
 //                       The store, the per-row bound rmax and the stop
 //                       position are staged to global memory.
 //   D vc_verify_kernel  (whole GPU, one thread per sample) proves that no
@@ -50,7 +50,7 @@
 // launched after every segment, empty unless the status says kDense); the
 // next segment continues after the chunk. Chunks double while the windows
 // between them stay dense. Windows adapt their length to where the store
-// fills. Decisions follow commit.hip's guard band (a margin within 1e-4 of its
+// fills. Decisions keep a guard band (dc::kGuard: a margin within 1e-4 of its
 // threshold is re-scored from the live model M0 + dW before the decision).
 //
 // Device state (int64 words, 512 B) lives in the kSerial scratch; every kernel
@@ -69,8 +69,8 @@ namespace vc {
 using dc::Geo;
 constexpr int kFCMax = 2;               // feature chunks of 16 per lane (a sample of <= 32 features)
 constexpr int kRec = 16 * kFCMax;       // feature slots of a candidate record
-constexpr int64_t kLwMin = 2048, kLwMax = 65536, kLwInit = 8192;
-constexpr int kBitWords = (int)(kLwMax / 64);
+constexpr int64_t kLwMin = 2048, kLwMax = kVcWindowMax, kLwInit = 8192;
+constexpr int kBitWords = kVcBitWords;
 // candidate rule (kernel A): slack0 <= T, T adapting (x1.5 on a
 // verification failure, x0.97 per committed window, >= kTMin). Measured on
 // the bench stream (tools/exact_study.py rules_w8192): at 0.125 the final
@@ -81,10 +81,7 @@ constexpr int kBitWords = (int)(kLwMax / 64);
 constexpr float kTInit = 0.5f, kTMin = 0.125f, kTMax = 64.f;
 constexpr int64_t kMagic = 0x56434f4d4d495433LL;
 constexpr int kRetryForce = 3;          // retries of one window before all its samples are candidates
-// (status, state words and stop reasons: jb_vc_state.hpp, shared with the stepper)
-static_assert(kTailReasonW == dc::kTailReason && kReasonDone == dc::kStopDone &&
-                  kReasonSaturated == dc::kStopSaturated,
-              "jb_vc_state.hpp mirrors jb_commit.hpp's tail words");
+// (status and state words: jb_vc_state.hpp, shared with the stepper)
 
 __device__ __forceinline__ float st_T(const int64_t* st) { return __int_as_float((int)st[S_T]); }
 __device__ __forceinline__ int64_t ld_st(const int64_t* p) {
@@ -175,14 +172,14 @@ __global__ __launch_bounds__(256) void vc_init_kernel(int64_t* __restrict__ st, 
   st[S_DENSE_PM] = dense_pm;
   st[S_DCHUNK] = kDenseChunk0;
   st[S_BBEG] = beg;
-  for (int i = 0; i < 32; ++i) tail[i] = 0;
-  tail[0] = beg < bend ? beg : bend;
-  tail[1] = bend;
-  tail[31] = 1;    // marker: the verified committer ran this batch
+  for (int i = 0; i < kTailWords; ++i) tail[i] = 0;
+  tail[kTailStart] = beg < bend ? beg : bend;
+  tail[kTailEnd] = bend;
+  tail[kTailVerified] = 1;    // marker: the verified committer ran this batch
 }
 
 // ------------------------------------------------------------ A: score + candidate bits
-// one wave per sample (lanes as Lanes<LC>, as delta_s0_kernel)
+// one wave per sample (lanes as Lanes<LC>)
 template <int LC>
 __device__ __forceinline__ void wave_score(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ fidx,
                                            const float* __restrict__ fval, const float* __restrict__ W,
@@ -1079,41 +1076,39 @@ __global__ __launch_bounds__(256) void vc_verify_kernel(
     st[S_VIOL] = 0;
     const int s2 = (int)st[S_STATUS];
     if (s2 != kRetry) st[S_WIDE] = 0;   // a retry keeps the window's candidates (and width)
-    tail[0] = s2 == kDone ? st[S_BEND] : st[S_BEG];
-    tail[1] = st[S_BEND];
-    tail[2] = st[S_STEPS];
-    tail[3] = st[S_ROUNDS];
+    tail[kTailStart] = s2 == kDone ? st[S_BEND] : st[S_BEG];
+    tail[kTailEnd] = st[S_BEND];
+    tail[kTailSteps] = st[S_STEPS];
+    tail[kTailRounds] = st[S_ROUNDS];
     // stop reason: done / saturated (segments ran out) / dense
-    tail[dc::kTailReason] = s2 == kDone ? dc::kStopDone : s2 == kDense ? dc::kStopDense : dc::kStopSaturated;
-    tail[21] = st[S_WINDOWS] + st[S_RETRIES];   // segments used
+    tail[kTailReason] = s2 == kDone ? kStopDone : s2 == kDense ? kStopDense : kStopSaturated;
+    tail[kTailSegments] = st[S_WINDOWS] + st[S_RETRIES];
     tail[kTailStepped] = st[S_STEPPED];
     tail[kTailChunks] = st[S_NCHUNK];
     tail[kTailSegEst] = seg_estimate(st);
     tail[kTailCsWindows] = st[S_CSN];
-    tail[22] = st[S_WASTED];
-    tail[23] = st[S_REFRESH];
-    tail[24] = st[S_UPD];
-    tail[25] = st[S_NSLOTS];
-    tail[26] = st[S_EXACT];
-    tail[27] = st[S_CAND];
-    tail[28] = st[S_RETRIES];
-    tail[29] = st[S_SAT];
-    tail[30] = st[S_TICKS];
-    for (int i = 0; i < 5; ++i) tail[10 + i] = st[S_PH0 + i];
-    tail[15] = st[S_PHW];
-    tail[8] = st[S_LW];
-    tail[9] = st[S_T];
-    tail[7] = st[S_NONC];
+    tail[kTailWasted] = st[S_WASTED];
+    tail[kTailRefresh] = st[S_REFRESH];
+    tail[kTailUpdates] = st[S_UPD];
+    tail[kTailRows] = st[S_NSLOTS];
+    tail[kTailExact] = st[S_EXACT];
+    tail[kTailCand] = st[S_CAND];
+    tail[kTailRetries] = st[S_RETRIES];
+    tail[kTailSatWindows] = st[S_SAT];
+    tail[kTailTicks] = st[S_TICKS];
+    for (int i = 0; i < 5; ++i) tail[kTailVcPhase0 + i] = st[S_PH0 + i];
+    tail[kTailVcPhaseWall] = st[S_PHW];
+    tail[kTailVcWindowLen] = st[S_LW];
+    tail[kTailVcT] = st[S_T];
+    tail[kTailVcNonCand] = st[S_NONC];
   }
 }
 
 }  // namespace vc
 }  // namespace jb
 
-// bytes of the verified committer's fixed region (after the per-sample arrays):
-// state (512 B), candidate bits, the staged store (keys, rmax, dW, dP)
-static constexpr int64_t kVcFixed = 512 + 8 * jb::vc::kBitWords + 4 * 1024 + 4 * 1024 + 2 * 4 * 16384;
-extern "C" int64_t jb_vcommit_fixed_bytes() { return kVcFixed; }
+// bytes of the verified committer's fixed region (jb_serial_layout.hpp)
+extern "C" int64_t jb_vcommit_fixed_bytes() { return jb::kVcFixed; }
 
 // stepper.hip
 extern "C" int jb_stepper_enabled();
@@ -1140,15 +1135,11 @@ static int launch_vc(int method, const int64_t* row_ptr, const int32_t* fidx, co
   }();
   // committer shape (samples per group x rounds in flight), for A/B runs:
   // JB_VC_SHAPE = r1pd1; default r1pd2 (measured: r1pd2 7.19, r1pd1 7.27,
-  // r1pd3 7.25, r2pd1 8.47, r2pd2 8.45 ms per steady 131 K batch)
-  static const int shape = [] {
+  // r1pd3 7.25, r2pd1 8.47, r2pd2 8.45 ms per steady 131 K batch; only the
+  // first two are compiled in)
+  static const bool r1pd1 = [] {
     const char* e = getenv("JB_VC_SHAPE");
-    if (e == nullptr) return 0;
-    if (strcmp(e, "r2pd2") == 0) return 1;
-    if (strcmp(e, "r2pd1") == 0) return 2;
-    if (strcmp(e, "r1pd1") == 0) return 3;
-    if (strcmp(e, "r1pd3") == 0) return 4;
-    return 0;
+    return e != nullptr && strcmp(e, "r1pd1") == 0;
   }();
   float* Pp = method >= jb::CW ? S : nullptr;
   for (int seg = 0; seg < nseg; ++seg) {
@@ -1162,7 +1153,7 @@ static int launch_vc(int method, const int64_t* row_ptr, const int32_t* fidx, co
   hipLaunchKernelGGL((vc_commit_kernel<L, M, R, PD, 2>), dim3(1), dim3(64), 0, stream, st, W, Pp, active, C, s0, \
                      aux, pp0, fi, fx, gk, gr, gdw, gdp, prof);
 #define JB_VC_M(M)                               \
-  if (shape == 3) { JB_VC_S(M, 1, 1) }           \
+  if (r1pd1) { JB_VC_S(M, 1, 1) }                \
   else { JB_VC_S(M, 1, 2) }                      \
   break;
     switch (method) {
@@ -1197,31 +1188,32 @@ static int launch_vc(int method, const int64_t* row_ptr, const int32_t* fidx, co
 }
 
 // Steps 1-2 of a kSerial batch for LC <= 64 with the verified committer; the
-// caller runs the exact single-stream kernel over [tail[0], tail[1]) afterwards
-// (empty when every window committed). scratch: [tail int64 x 32][S0: n_max x
-// 64 floats][PP0: n_max x 32 float2][FI: n_max x 32][FX: n_max x 32][AUX: n_max
-// int4][SL: n_max floats][fixed region, 256-aligned: state, bits, staged store]
+// caller runs the exact single-stream kernel over [tail[kTailStart],
+// tail[kTailEnd]) afterwards (empty when every window committed). scratch: the
+// tail words, the per-sample arrays and the fixed region of jb_serial_layout.hpp
 extern "C" int jb_vcommit_prepare(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
                                   const int32_t* labels, const int64_t* stream_ptr, int nstreams, int64_t n_max,
                                   float* W, float* S, const int32_t* active, int LC, int method, float C,
                                   unsigned long long* stats, uint8_t* touched, void* scratch, int nseg,
                                   hipStream_t stream) {
   if (LC > 64) return -1;
+  using Lay = jb::VcScratch;
   int64_t* tail = (int64_t*)scratch;
-  uint8_t* base = (uint8_t*)scratch + 256;
-  float* s0 = (float*)base;
-  float2* pp0 = (float2*)(base + 256 * n_max);
-  int32_t* fi = (int32_t*)(base + 512 * n_max);
-  float* fx = (float*)(base + 640 * n_max);
-  int4* aux = (int4*)(base + 768 * n_max);
-  float* sl = (float*)(base + 784 * n_max);
-  uint8_t* fixed = base + ((788 * n_max + 255) & ~(int64_t)255);
+  uint8_t* base = (uint8_t*)scratch;
+  float* s0 = (float*)(base + Lay::offset(Lay::S0, n_max));
+  float2* pp0 = (float2*)(base + Lay::offset(Lay::PP0, n_max));
+  int32_t* fi = (int32_t*)(base + Lay::offset(Lay::FI, n_max));
+  float* fx = (float*)(base + Lay::offset(Lay::FX, n_max));
+  int4* aux = (int4*)(base + Lay::offset(Lay::AUX, n_max));
+  float* sl = (float*)(base + Lay::offset(Lay::SL, n_max));
+  // the fixed region: state words, candidate bits, staged store (keys, rmax, dW, dP)
+  uint8_t* fixed = base + Lay::fixed_offset(n_max);
   int64_t* st = (int64_t*)fixed;
-  unsigned long long* bits = (unsigned long long*)(fixed + 512);
-  int32_t* gk = (int32_t*)(fixed + 512 + 8 * jb::vc::kBitWords);
-  float* gr = (float*)((uint8_t*)gk + 4 * 1024);
-  float* gdw = (float*)((uint8_t*)gr + 4 * 1024);
-  float* gdp = gdw + 16384;
+  unsigned long long* bits = (unsigned long long*)(fixed + jb::kVcStateBytes);
+  int32_t* gk = (int32_t*)(bits + jb::kVcBitWords);
+  float* gr = (float*)(gk + jb::kVcStoreRows);
+  float* gdw = gr + jb::kVcStoreRows;
+  float* gdp = gdw + jb::kVcStoreFloats;
   // JB_VERIFIED_T: the candidate threshold at every batch start (tests force
   // verification failures with a tiny one); unset: T adapts across batches
   const char* te = getenv("JB_VERIFIED_T");

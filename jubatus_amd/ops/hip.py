@@ -740,6 +740,22 @@ def linear_train(row_ptr: torch.Tensor, fidx: torch.Tensor, fval: torch.Tensor,
     _check(rc, "jb_linear_train")
 
 
+# The 32 tail words (int64 each) at the start of the serial scratch, by name:
+# the enum of csrc/hip/jb_serial_layout.hpp (tests/test_serial_layout.py holds
+# this table and the header together)
+TAIL_WORDS = {
+    "kTailStart": 0, "kTailEnd": 1, "kTailSteps": 2, "kTailRounds": 3,
+    "kTailBoundPhase0": 4, "kTailVcNonCand": 7, "kTailVcWindowLen": 8, "kTailVcT": 9,
+    "kTailBoundWall": 10, "kTailVcPhase0": 10, "kTailBoundCycles": 11, "kTailBoundWave0": 12,
+    "kTailVcPhaseWall": 15, "kTailStepped": 16, "kTailChunks": 17, "kTailSegEst": 18,
+    "kTailCsWindows": 19, "kTailReason": 20, "kTailSegments": 21, "kTailWasted": 22,
+    "kTailRefresh": 23, "kTailUpdates": 24, "kTailRows": 25, "kTailExact": 26, "kTailCand": 27,
+    "kTailRetries": 28, "kTailSatWindows": 29, "kTailTicks": 30, "kTailVerified": 31,
+    "kTailWords": 32,
+}
+STOP_REASONS = ("done", "saturated", "dense", "rescore")    # kStopDone .. kStopRescore
+
+
 class SerialScratch:
     """device scratch of the serial-equivalent train mode (csrc/hip/serial.hip:
     the committer's tail range and the per-sample slack), grown on demand.
@@ -755,49 +771,52 @@ class SerialScratch:
         left to the sequential kernel, batch end, exact steps, rounds"""
         if self.buf is None:
             return {}
-        v = self.buf[:256].view(torch.int64).tolist()
-        reasons = ("done", "saturated", "dense", "rescore")
-        out = {"tail_start": v[0], "end": v[1], "exact_steps": v[2], "rounds": v[3],
-               "segments": v[21], "stop_reason": reasons[v[20]] if 0 <= v[20] < 4 else v[20]}
-        if v[31] == 1:
+        v = self.buf[:8 * TAIL_WORDS["kTailWords"]].view(torch.int64).tolist()
+
+        def w(name, i=0):
+            return v[TAIL_WORDS[name] + i]
+
+        why = w("kTailReason")
+        out = {"tail_start": w("kTailStart"), "end": w("kTailEnd"), "exact_steps": w("kTailSteps"),
+               "rounds": w("kTailRounds"), "segments": w("kTailSegments"),
+               "stop_reason": STOP_REASONS[why] if 0 <= why < len(STOP_REASONS) else why}
+        if w("kTailVerified") == 1:
             # verified committer (csrc/hip/vcommit.hip): windows, verification
             # retries, candidates the committer walked, non-candidates cleared
             # by the bound, the window length / threshold T it ends with
             import struct
-            out.update(verified=True, windows=v[21] - v[28], retries=v[28], saturated_windows=v[29],
-                       candidates=v[27], non_candidates_verified=v[7], committer_updates=v[24],
-                       wasted_steps=v[22], refreshes=v[23], exact_rescored=v[26], last_segment_rows=v[25],
-                       window_len=v[8], T=round(struct.unpack("f", struct.pack("I", v[9] & 0xffffffff))[0], 4),
-                       commit_kernel_us=round(v[30] / 100.0, 1),
+            ticks = w("kTailTicks")
+            out.update(verified=True, windows=w("kTailSegments") - w("kTailRetries"), retries=w("kTailRetries"),
+                       saturated_windows=w("kTailSatWindows"), candidates=w("kTailCand"),
+                       non_candidates_verified=w("kTailVcNonCand"), committer_updates=w("kTailUpdates"),
+                       wasted_steps=w("kTailWasted"), refreshes=w("kTailRefresh"),
+                       exact_rescored=w("kTailExact"), last_segment_rows=w("kTailRows"),
+                       window_len=w("kTailVcWindowLen"),
+                       T=round(struct.unpack("f", struct.pack("I", w("kTailVcT") & 0xffffffff))[0], 4),
+                       commit_kernel_us=round(ticks / 100.0, 1),
                        # samples the sequential stepper (csrc/hip/stepper.hip)
                        # applied: chunks after update-dense windows, and the
                        # rest the segments left (stop_reason "dense")
-                       stepper_samples=v[16] + v[1] - v[0], stepper_chunks=v[17],
+                       stepper_samples=w("kTailStepped") + w("kTailEnd") - w("kTailStart"),
+                       stepper_chunks=w("kTailChunks"),
                        # windows whose candidates the stepper walked (kernel C's place)
-                       stepper_windows=v[19])
-            if v[15] > 0:      # JB_COMMIT_PROF=1: committer phases (shader cycles -> us by the wall clock)
-                us = (v[30] / 100.0) / v[15]
+                       stepper_windows=w("kTailCsWindows"))
+            if w("kTailVcPhaseWall") > 0:   # JB_COMMIT_PROF=1: committer phases (shader cycles -> us by the wall clock)
+                us = (ticks / 100.0) / w("kTailVcPhaseWall")
                 for i, nm in enumerate(("round_start", "select", "decide", "apply", "correct")):
-                    out[f"commit_{nm}_us"] = round(v[10 + i] * us, 1)
+                    out[f"commit_{nm}_us"] = round(w("kTailVcPhase0", i) * us, 1)
             return out
-        if v[24] > 0 or v[22] > 0:
-            # delta committer (csrc/hip/commit.hip): steps that did not update,
-            # guard-band re-scores, updates, rows in the LDS store at the end
-            out.update(wasted_steps=v[22], refreshes=v[23], committer_updates=v[24],
-                       last_segment_rows=v[25])
-            if v[27] > 0:     # counted with the phase stamps only (JB_COMMIT_PROF=1)
-                out.update(exact_rescored=v[26], committed_samples=v[27])
-        # committer phases in shader cycles, scaled to us by the wall clock
-        wall_us = v[10] / 100.0
-        if v[11] > 0:
-            us = wall_us / v[11]
+        # bound committer (csrc/hip/serial.hip, label capacities > 64) built
+        # with JB_SERIAL_TIMING=1: its phases in shader cycles, scaled to us by
+        # the wall clock
+        if w("kTailBoundCycles") > 0:
+            wall_us = w("kTailBoundWall") / 100.0
+            us = wall_us / w("kTailBoundCycles")
             out["commit_us"] = round(wall_us, 1)
-            names = (("start", "barrier_a", "step", "corr", "flush", "init") if "committer_updates" in out
-                     else ("bound", "barrier_a", "stage_b1", "step", "barrier_b2", "round"))
-            for i, nm in enumerate(names):
-                out[f"commit_{nm}_us"] = round(v[4 + i] * us, 1)
-            for w in range(8):     # per wave: round-start bounds + post-step work
-                out[f"commit_wave{w}_work_us"] = round(v[12 + w] * us, 1)
+            for i, nm in enumerate(("bound", "barrier_a", "stage_b1", "step", "barrier_b2", "round")):
+                out[f"commit_{nm}_us"] = round(w("kTailBoundPhase0", i) * us, 1)
+            for k in range(8):     # per wave: round-start bounds + post-step work
+                out[f"commit_wave{k}_work_us"] = round(w("kTailBoundWave0", k) * us, 1)
         return out
 
     def ptr(self, n_max: int, lc: int = 0) -> int:

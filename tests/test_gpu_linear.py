@@ -467,10 +467,11 @@ def test_serial_mode_matches_oracle(method):
 
 @pytest.mark.parametrize("method", ["PA1", "AROW"])
 def test_serial_mode_big_batch_rescores(method):
-    """one batch of >= 16384 samples (csrc/hip/serial.hip kSerialBigBatch):
-    the committer ends a segment once kRescoreWaste exact steps did not
-    update and the next segment re-scores the rest against the live model -
-    the result must still be the requests applied one after the other"""
+    """one batch of >= 16384 samples (csrc/hip/serial.hip kSerialBigBatch) at
+    6 labels: the verified committer (csrc/hip/vcommit.hip) takes it in
+    several segments, each a window scored against the live model, with the
+    segment budget of a big batch - the result must still be the requests
+    applied one after the other"""
     from jubatus_amd.models.classifier import LinearClassifier
 
     param = {"regularization_weight": 0.5}
@@ -592,6 +593,65 @@ def test_serial_mode_every_sample_updates(nlabels):
     g.synchronize()
     st = g.train_stats()
     assert st["updated"] == c.train_stats()["updated"] and st["updated"] > 0.5 * len(data)
+    scale = float(np.abs(c.W).max()) or 1.0
+    np.testing.assert_allclose(g.W.cpu().numpy()[:, :c.LC], c.W, rtol=2e-3, atol=2e-3 * scale)
+    np.testing.assert_allclose(g.P.cpu().numpy()[:, :c.LC], c.P, rtol=2e-3,
+                               atol=2e-3 * float(c.P.max()))
+
+
+# warm-up requests of test_serial_mode_bound_settles_sparse_stream. Measured
+# share of the batch the committer settled, by warm-up: 160 requests 0.56,
+# 240 0.66, 320 and 480 1.00 (170 exact steps, the bound settles the rest)
+BOUND_WARM_REQS = 320
+
+
+def _bound_sparse_stream(warm_reqs, nbatch_reqs=64, per_req=40):
+    """70 registered labels (label capacity 128: the bound committer of
+    csrc/hip/serial.hip), samples from 6 of them, a warm-up trained request by
+    request and one concurrent batch. Returns (gpu model, oracle, samples of
+    the batch, diagnostics of the batch)."""
+    from jubatus_amd.models.classifier import LinearClassifier
+
+    param = {"regularization_weight": 0.5}
+    rng = random.Random(41)
+    data = []                            # the stream of test_serial_mode_big_batch_rescores
+    for _ in range((warm_reqs + nbatch_reqs) * per_req):
+        y = rng.randrange(6)
+        sv = [[f"s{j}", f"v{y * 7 + rng.randrange(3) if rng.random() < 0.9 else rng.randrange(300)}"]
+              for j in range(4)]
+        nv = [[f"n{j}", (y - 2) * 0.5 + rng.gauss(0, 1)] for j in range(3)] + [["bias", 1.0]]
+        data.append((f"L{y}", [sv, nv, []]))
+    reqs = [data[i:i + per_req] for i in range(0, len(data), per_req)]
+    g = LinearClassifier("AROW", param, DatumToFvConverter(CONV), device=_device())
+    c = LinearClassifier("AROW", param, DatumToFvConverter(CONV))
+    for m in (g, c):
+        for y in range(70):
+            m.set_label(f"L{y}")
+    for r in reqs[:warm_reqs]:
+        g.train(r)
+        c.train(r)
+    g.train_requests([msgpack.packb([[l, d] for l, d in r], use_bin_type=False) for r in reqs[warm_reqs:]])
+    for r in reqs[warm_reqs:]:
+        c.train(r)
+    g.synchronize()
+    g.pipe.check_errors()
+    return g, c, nbatch_reqs * per_req, g._serial.last_batch()
+
+
+def test_serial_mode_bound_settles_sparse_stream():
+    """label capacity 128 on a stream that mostly does not update: the bound
+    committer (csrc/hip/serial.hip serial_score_kernel / serial_commit_kernel)
+    settles at least half of the batch itself, before any sequential tail, and
+    the result is the requests applied one after the other"""
+    g, c, nbatch, diag = _bound_sparse_stream(BOUND_WARM_REQS)
+    print(diag)
+    assert c.LC == 128 and g.W.shape[1] == 128
+    assert not diag.get("verified"), diag
+    first = diag["end"] - nbatch
+    assert diag["tail_start"] - first >= 0.5 * nbatch, diag
+    st = g.train_stats()
+    assert st["trained"] == BOUND_WARM_REQS * 40 + nbatch
+    assert st["updated"] == c.train_stats()["updated"], (st, c.train_stats())
     scale = float(np.abs(c.W).max()) or 1.0
     np.testing.assert_allclose(g.W.cpu().numpy()[:, :c.LC], c.W, rtol=2e-3, atol=2e-3 * scale)
     np.testing.assert_allclose(g.P.cpu().numpy()[:, :c.LC], c.P, rtol=2e-3,

@@ -1,7 +1,7 @@
 """Host study of the serial-equivalent (exact) training on the bench's stream:
 how many samples of a batch could update, and how far the rest stay from
 their threshold, under the bound the GPU committer verifies
-(csrc/hip/commit.hip: a sample whose slack at the segment start exceeds
+(csrc/hip/vcommit.hip: a sample whose slack at the segment start exceeds
 2 sum_f |x_f| R_f - R_f the summed step magnitudes of row f in the segment -
 cannot update there).
 

@@ -6,11 +6,25 @@
 //   running mean / variance of the targets (count, sum, sum of squares)
 //   err = y - w.x,  loss = |err| - sensitivity * stddev
 //   loss > 0:  w += sign(err) * min(C, loss) / ||x||^2 * x
+// Slots with idx < 0 (unmatched converter rules) are skipped. An index that
+// occurs several times in one sample (a repeated key, a hash collision)
+// counts once per occurrence in w.x, in ||x||^2 and in the update: every
+// increment lands, in both modes (tests/test_gpu_regression.py).
 //
 // One wave64 per update stream (see linear.hip for the stream model); the
-// lanes own features. Exact mode (one stream): plain stores drained before
-// the next sample and the target statistics carried in registers. Concurrent
-// streams: float atomics for w and for the statistics deltas.
+// lanes own features. The w update is a float atomic add in both modes, so
+// lanes that hold the same index cannot lose each other's increment. Exact
+// mode (one stream): the adds are drained before the next sample reads w,
+// which therefore sees its predecessor's w, and the target statistics are
+// carried in registers. Concurrent streams: no drain, and atomics for the statistics
+// deltas. A concurrent wave reads the global statistics ONCE, when it
+// starts, while waves that finished earlier may already have added their
+// deltas: with sensitivity > 0 the stddev a stream sees, and so its updates,
+// depend on launch timing (by design; sensitivity == 0 is deterministic up
+// to the order of the float adds).
+//
+// Known limit: the statistics are fp32 sums, and sum2/count - mean^2 cancels;
+// the stddev is lost once |mean| / stddev reaches a few thousand.
 #include "jb_device.hpp"
 
 namespace jb {
@@ -28,6 +42,8 @@ __global__ __launch_bounds__(256) void regression_train_kernel(
   const int lane = threadIdx.x & 63;
   const int wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (wid >= nstreams) return;
+  // CONC: a snapshot taken at this wave's start; earlier-finishing waves of
+  // the same launch may or may not be in it (timing-dependent for eps > 0)
   float sum = stats[0], sq = stats[1], cnt = stats[2];
   float dsum = 0.f, dsq = 0.f, dcnt = 0.f;
   for (int64_t s = stream_ptr[wid]; s < stream_ptr[wid + 1]; ++s) {
@@ -35,19 +51,22 @@ __global__ __launch_bounds__(256) void regression_train_kernel(
     const int n = (int)(row_ptr[s + 1] - beg);
     float dot = 0.f, nrm = 0.f;
     int32_t idx0 = -1;
-    float x0 = 0.f, w0 = 0.f;
+    float x0 = 0.f;
     for (int base = 0; base < n; base += 64) {
       const int j = base + lane;
-      if (j < n) {
-        const int32_t idx = fidx[beg + j];
-        const float x = fval[beg + j];
-        if (idx >= 0) {
-          const float w = ld_agent_r(W + idx);
-          dot += x * w;
-          nrm += x * x;
-          if (base == 0) { idx0 = idx; x0 = x; w0 = w; }
-        }
+      int32_t idx = -1;
+      float x = 0.f;
+      if (j < n) { idx = fidx[beg + j]; x = fval[beg + j]; }
+      // exact mode: the previous sample's adds are drained here, before the
+      // first read of w, so they complete behind this sample's row_ptr /
+      // fidx / fval loads and not in front of them
+      if (!CONC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (idx >= 0) {
+        const float w = ld_agent_r(W + idx);
+        dot += x * w;
+        nrm += x * x;
       }
+      if (base == 0) { idx0 = idx; x0 = x; }
     }
     dot = wave_sum(dot);
     nrm = wave_sum(nrm);
@@ -64,17 +83,12 @@ __global__ __launch_bounds__(256) void regression_train_kernel(
     for (int base = 0; base < n; base += 64) {
       const int j = base + lane;
       if (j >= n) continue;
-      int32_t idx; float x, w;
-      if (base == 0) { idx = idx0; x = x0; w = w0; }
-      else {
-        idx = fidx[beg + j]; x = fval[beg + j];
-        w = idx >= 0 ? ld_agent_r(W + idx) : 0.f;
-      }
+      int32_t idx; float x;
+      if (base == 0) { idx = idx0; x = x0; }
+      else { idx = fidx[beg + j]; x = fval[beg + j]; }
       if (idx < 0) continue;
-      if (CONC) atomicAdd(W + idx, coeff * x);
-      else W[idx] = w + coeff * x;
+      atomicAdd(W + idx, coeff * x);   // per occurrence: equal indices on two lanes both land
     }
-    if (!CONC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   if (lane == 0) {
     if (CONC) {

@@ -9,6 +9,8 @@ Rule (also the numerical oracle of csrc/hip/regression.hip):
     count, sum, sum2 of the targets; sd = sqrt(max(0, sum2/count - (sum/count)^2))
     err = y - w.x ; loss = |err| - sensitivity * sd
     loss > 0:  w += sign(err) * min(C, loss) / ||x||^2 * x
+    an index repeated inside a sample counts once per occurrence, in w.x, in
+    ||x||^2 and in the update
 
 Storage: w[H] (hashed features) in HBM on a GPU, NumPy otherwise.
 MIX: all-reduce mean of w and of the target statistics.
@@ -47,7 +49,8 @@ def train_one(w: np.ndarray, stats: np.ndarray, idx, val, y: float, C: float, ep
     nrm = float((x * x).sum())
     if loss > 0 and nrm > 0:
         coeff = sgn * min(C, loss) / nrm
-        w[idx] = w[idx] + np.float32(coeff) * x
+        # per occurrence: an index repeated inside the sample takes every increment
+        np.add.at(w, idx, np.float32(coeff) * x)
 
 
 class PARegression:

@@ -308,6 +308,65 @@ def test_native_regression_matches_oracle_and_files(tmp_path):
             p.kill()
 
 
+def test_native_regression_wide_and_repeated_keys_match_oracle(tmp_path):
+    """native jubaregression, request after request (one update stream per
+    launch: the exact-mode kernel): datums of 100 num keys (more than one
+    64-lane chunk) and datums that repeat a num key (one hashed index on two
+    slots, every occurrence counts) estimate as the host oracle does"""
+    from jubatus_amd.client import Regression
+    from jubatus_amd.fv_converter.converter import DatumToFvConverter, device_hash_max_size
+    from jubatus_amd.models.regression import PARegression
+    cfg_file = config_path("regression/pa.json")
+    cfg = json.load(open(cfg_file))
+    rng = random.Random(6)
+    coef = [rng.gauss(0, 1) for _ in range(100)]
+
+    def datum(i):
+        d = Datum()
+        if i % 2:
+            xs = [rng.gauss(0, 0.1) for _ in range(100)]
+            for j, x in enumerate(xs):
+                d.add(f"n{j}", x)
+            return sum(c * x for c, x in zip(coef, xs)) + rng.gauss(0, 0.1), d
+        xs = [rng.gauss(0, 1) for _ in range(3)] + [0.5 + rng.random()]
+        for j, x in enumerate(xs[:3]):
+            d.add(f"n{j}", x)
+        d.add("bias", 1.0)
+        d.add("n0", xs[3])                       # the key of the first slot again
+        return sum(c * x for c, x in zip(coef, xs[:3])) + coef[0] * xs[3] + 1.0 + rng.gauss(0, 0.1), d
+
+    data = [datum(i) for i in range(120)]
+    port = _free_port()
+    p = subprocess.Popen([REG_BIN, "-p", str(port), "-b", "127.0.0.1", "-f", cfg_file, "-d", str(tmp_path)],
+                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    try:
+        deadline = time.time() + 60
+        while True:
+            try:
+                with RpcClient("127.0.0.1", port, 5.0) as c:
+                    c.call("get_config", "")
+                break
+            except (OSError, RpcIOError, RpcTimeoutError):
+                assert p.poll() is None and time.time() < deadline, p.stdout.read()
+                time.sleep(0.2)
+        c = Regression("127.0.0.1", port, "", timeout=60)
+        ora = PARegression("PA", cfg.get("parameter"),
+                           DatumToFvConverter(cfg["converter"], default_hash_max_size=device_hash_max_size()),
+                           device=None)
+        for i in range(0, 100, 4):
+            assert c.train(data[i:i + 4]) == 4
+            ora.train([(s, d) for s, d in data[i:i + 4]])
+        test = [d for _, d in data[100:]]
+        np.testing.assert_allclose(c.estimate(test), ora.estimate(test), rtol=1e-4, atol=1e-4)
+        c.close()
+    finally:
+        p.terminate()
+        try:
+            p.wait(timeout=30)
+        except subprocess.TimeoutExpired:
+            p.kill()
+
+
 @pytest.mark.parametrize("cfg_name", ["classifier/default.json", "classifier/arow_combinational_feature.json"])
 def test_native_wide_converter_configs_match_oracle(cfg_name, tmp_path):
     """the reference's default classifier config (bigram tokens, tf / idf

@@ -1,4 +1,6 @@
-// Online passive-aggressive regression on a hashed weight vector in HBM.
+// Online regression on a hashed weight vector in HBM: passive-aggressive
+// (PA, the reference's only method) and, with rules defined by this project,
+// PA1, PA2, perceptron, CW, AROW and NHERD.
 //
 // Reference: the regression engine's train/estimate loops,
 // jubatus/server/server/regression_serv.cpp:123-149, over jubatus_core's PA
@@ -10,6 +12,25 @@
 // occurs several times in one sample (a repeated key, a hash collision)
 // counts once per occurrence in w.x, in ||x||^2 and in the update: every
 // increment lands, in both modes (tests/test_gpu_regression.py).
+//
+// The other six methods (regression_train_m_kernel) are the classifier's
+// formulas (models/linear_oracle.py) with one label, no rival label and
+// 1 - margin replaced by loss. The reference (Jubatus 0.9.2) ships PA
+// regression only, so these rules are this project's own, their oracle is
+// models/regression.py, and parity with later Jubatus releases is unpinned.
+// With S = 1/P (P: diagonal precision, initial value 1), v = sum x^2 S:
+//   PA1         tau = min(C, loss / ||x||^2)          w += sgn tau x
+//   PA2         tau = loss / (||x||^2 + 1/(2C))
+//   perceptron  tau = learning rate
+//   AROW        beta = 1 / (v + 1/C), alpha = loss beta
+//               w += sgn alpha S x,  P += beta x^2 / (1 - beta S x^2)
+//   NHERD       alpha = loss / (v + 1/C), beta = (C^2 v + 2C) / (1 + C v)^2
+//   CW          m = -loss, phi = C, b = 1 + 2 phi m,
+//               gamma = (-b + sqrt(max(0, b^2 - 8 phi (m - phi v)))) / (4 phi v) > 0
+//               w += sgn gamma S x,  P += 2 gamma phi x^2
+// all but CW when loss > 0 and ||x||^2 > 0; CW when v > 0 and gamma > 0.
+// Every occurrence's increment, on w and on P, is computed from the P the
+// sample found (gather, compute, scatter).
 //
 // One wave64 per update stream (see linear.hip for the stream model); the
 // lanes own features. The w update is a float atomic add in both modes, so
@@ -25,7 +46,7 @@
 //
 // Known limit: the statistics are fp32 sums, and sum2/count - mean^2 cancels;
 // the stddev is lost once |mean| / stddev reaches a few thousand.
-#include "jb_device.hpp"
+#include "jb_linear.hpp"
 
 namespace jb {
 
@@ -119,6 +140,205 @@ __global__ __launch_bounds__(256) void regression_estimate_kernel(
   if (lane == 0) out[s] = dot;
 }
 
+// ------------------------------------------------- the methods besides PA
+// step sizes of one sample (M: Method of jb_linear.hpp): w += sgn tau (S) x,
+// P increments from beta (dprec); false when the sample causes no update
+template <int M>
+__device__ __forceinline__ bool regression_step(float loss, float nrm, float var, float C,
+                                                float* tau, float* beta) {
+  *beta = 0.f;
+  if (M == CW) {
+    if (!(var > 0.f)) return false;
+    const float m = -loss, phi = C;
+    const float b = 1.f + 2.f * phi * m;
+    const float gamma = (-b + sqrtf(fmaxf(0.f, b * b - 8.f * phi * (m - phi * var)))) / (4.f * phi * var);
+    if (!(gamma > 0.f)) return false;
+    *tau = gamma;
+    *beta = 2.f * gamma * phi;
+    return true;
+  }
+  if (!(loss > 0.f) || !(nrm > 0.f)) return false;
+  if (M == PA1) {
+    *tau = fminf(C, loss / nrm);
+  } else if (M == PA2) {
+    *tau = loss / (nrm + 0.5f / C);
+  } else if (M == PERCEPTRON) {
+    *tau = C;                                   // the learning rate
+  } else if (M == AROW) {
+    *beta = 1.f / (var + 1.f / C);
+    *tau = loss * *beta;
+  } else {                                      // NHERD
+    *tau = loss / (var + 1.f / C);
+    const float cv = 1.f + C * var;
+    *beta = (C * C * var + 2.f * C) / (cv * cv);
+  }
+  return true;
+}
+
+// slots of a sample whose idx, x and pre-sample P stay in registers between
+// the gather and the scatter: kRegChunks chunks of 64
+constexpr int kRegChunks = 4;
+constexpr int kRegSlots = kRegChunks * 64;
+
+// PA1 / PA2 / perceptron / CW / AROW / NHERD, same stream model and idioms as
+// regression_train_kernel. The confidence methods (COV) gather 1/P with w.
+//
+// The pre-sample-P rule: every occurrence's w step and P increment take the P
+// the sample found, also when the index occurs again in another chunk. The
+// first kRegSlots slots keep idx, x and P in registers, so their scatter reads
+// nothing. A wider sample's remaining slots read P again, which is only
+// sound while no P add of this sample has been issued: their w steps go first
+// and their P increments are parked in slot_scratch[beg + j] (one float per
+// slot, the caller's), then the register slots scatter, then the parked
+// increments are added. A wide sample without slot_scratch is a caller
+// error: the stream stops there and its statistics become NaN (nothing is
+// written through the null pointer).
+//
+// Concurrent streams, confidence methods: a slot whose index is unique among
+// the register slots adds its P increment first with a returning atomic and
+// steps w with the returned P, the variance at this update's place in the
+// row's atomic order (linear.hip "Serialized confidence" has the reason; one
+// stream gets back the value it gathered). Repeated slots and the slots past
+// the registers keep the gathered value.
+template <int M, bool CONC>
+__global__ __launch_bounds__(256) void regression_train_m_kernel(
+    const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ fidx,
+    const float* __restrict__ fval, const float* __restrict__ targets,
+    const int64_t* __restrict__ stream_ptr, int nstreams, float* W, float* P, float* stats,
+    float* slot_scratch, float C, float eps) {
+  constexpr bool COV = M >= CW;
+  const int lane = threadIdx.x & 63;
+  const int wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (wid >= nstreams) return;
+  float sum = stats[0], sq = stats[1], cnt = stats[2];
+  float dsum = 0.f, dsq = 0.f, dcnt = 0.f;
+  for (int64_t s = stream_ptr[wid]; s < stream_ptr[wid + 1]; ++s) {
+    const int64_t beg = row_ptr[s];
+    const int n = (int)(row_ptr[s + 1] - beg);
+    if (COV && n > kRegSlots && slot_scratch == nullptr) {
+      sum = dsum = __builtin_nanf("");
+      break;
+    }
+    float dot = 0.f, nrm = 0.f, var = 0.f;
+    int32_t ri[kRegChunks];
+    float rx[kRegChunks], rp[kRegChunks];
+#pragma unroll
+    for (int c = 0; c < kRegChunks; ++c) {
+      ri[c] = -1; rx[c] = 0.f; rp[c] = 1.f;
+      if (c * 64 < n) {
+        const int j = c * 64 + lane;
+        if (j < n) { ri[c] = fidx[beg + j]; rx[c] = fval[beg + j]; }
+        // exact mode: the previous sample's adds, on w and on P, are drained
+        // before this sample's first table read (as regression_train_kernel)
+        if (!CONC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (ri[c] >= 0) {
+          const float w = ld_agent_r(W + ri[c]);
+          if (COV) rp[c] = ld_agent_r(P + ri[c]);
+          const float x2 = rx[c] * rx[c];
+          dot += rx[c] * w;
+          nrm += x2;
+          if (COV) var += x2 * (1.f / rp[c]);
+        }
+      }
+    }
+    for (int base = kRegSlots; base < n; base += 64) {
+      const int j = base + lane;
+      if (j >= n) continue;
+      const int32_t idx = fidx[beg + j];
+      if (idx < 0) continue;
+      const float x = fval[beg + j];
+      const float w = ld_agent_r(W + idx);
+      dot += x * w;
+      nrm += x * x;
+      if (COV) var += x * x * (1.f / ld_agent_r(P + idx));
+    }
+    dot = wave_sum(dot);
+    nrm = wave_sum(nrm);
+    if (COV) var = wave_sum(var);
+    const float y = targets[s];
+    sum += y; sq += y * y; cnt += 1.f;
+    dsum += y; dsq += y * y; dcnt += 1.f;
+    const float avg = sum / cnt;
+    const float sd = sqrtf(fmaxf(0.f, sq / cnt - avg * avg));
+    const float err = y - dot;
+    const float sgn = err > 0.f ? 1.f : -1.f;
+    const float loss = sgn * err - eps * sd;
+    float tau = 0.f, beta = 0.f;
+    if (!regression_step<M>(loss, nrm, var, C, &tau, &beta)) continue;
+    const float coeff = sgn * tau;
+    if (!COV) {
+#pragma unroll
+      for (int c = 0; c < kRegChunks; ++c)
+        if (ri[c] >= 0) atomicAdd(W + ri[c], coeff * rx[c]);   // per occurrence
+      for (int base = kRegSlots; base < n; base += 64) {
+        const int j = base + lane;
+        if (j >= n) continue;
+        const int32_t idx = fidx[beg + j];
+        if (idx >= 0) atomicAdd(W + idx, coeff * fval[beg + j]);
+      }
+      continue;
+    }
+    // 1. slots past the registers: P is still as the sample found it
+    for (int base = kRegSlots; base < n; base += 64) {
+      const int j = base + lane;
+      if (j >= n) continue;
+      const int32_t idx = fidx[beg + j];
+      if (idx < 0) continue;
+      const float x = fval[beg + j];
+      const float sv = 1.f / ld_agent_r(P + idx);
+      atomicAdd(W + idx, coeff * sv * x);
+      slot_scratch[beg + j] = dprec(M, beta, x, sv);
+    }
+    // every P read of step 1 has returned (and every parked increment is
+    // written) before the first P add below is issued
+    if (n > kRegSlots) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // 2. register slots
+    bool dup[kRegChunks];
+#pragma unroll
+    for (int c = 0; c < kRegChunks; ++c) dup[c] = !CONC;
+    if (CONC) {
+#pragma unroll
+      for (int c = 0; c < kRegChunks; ++c) {
+        const int m = min(64, n - c * 64);
+        for (int j = 0; j < m; ++j) {
+          const int32_t ij = __builtin_amdgcn_readlane(ri[c], j);
+#pragma unroll
+          for (int d = 0; d < kRegChunks; ++d) dup[d] |= ij == ri[d] && !(c == d && j == lane);
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < kRegChunks; ++c) {
+      if (ri[c] < 0) continue;
+      const float sv = 1.f / rp[c];
+      const float dp = dprec(M, beta, rx[c], sv);
+      if (CONC && !dup[c]) {
+        const float pr = atomicAdd(P + ri[c], dp);
+        atomicAdd(W + ri[c], coeff * rx[c] / pr);
+      } else {
+        atomicAdd(W + ri[c], coeff * sv * rx[c]);
+        atomicAdd(P + ri[c], dp);
+      }
+    }
+    // 3. the parked increments
+    for (int base = kRegSlots; base < n; base += 64) {
+      const int j = base + lane;
+      if (j >= n) continue;
+      const int32_t idx = fidx[beg + j];
+      if (idx >= 0) atomicAdd(P + idx, ld_agent_r(slot_scratch + beg + j));
+    }
+  }
+  if (lane == 0) {
+    if (CONC) {
+      atomicAdd(stats + 0, dsum);
+      atomicAdd(stats + 1, dsq);
+      atomicAdd(stats + 2, dcnt);
+    } else {
+      stats[0] = sum; stats[1] = sq; stats[2] = cnt;
+    }
+  }
+}
+
 }  // namespace jb
 
 extern "C" int jb_regression_train(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
@@ -133,6 +353,47 @@ extern "C" int jb_regression_train(const int64_t* row_ptr, const int32_t* fidx, 
   else
     hipLaunchKernelGGL(jb::regression_train_kernel<false>, dim3(blocks), dim3(threads), 0, stream,
                        row_ptr, fidx, fval, targets, stream_ptr, nstreams, W, stats, C, eps);
+  return (int)hipGetLastError();
+}
+
+// method: models/linear_oracle.py METHOD_IDS (Method of jb_linear.hpp). PA
+// launches regression_train_kernel, exactly as jb_regression_train does. C is
+// the regularization weight (perceptron: the learning rate). P: the precision
+// table of CW / AROW / NHERD, null otherwise. slot_scratch: as many floats as
+// fval, for those three methods; may be null when no sample has more than 256
+// slots.
+extern "C" int jb_regression_train_m(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
+                                     const float* targets, const int64_t* stream_ptr, int nstreams,
+                                     float* W, float* P, float* stats, float* slot_scratch,
+                                     int method, float C, float eps, int concurrent,
+                                     hipStream_t stream) {
+  if (method == jb::PA)
+    return jb_regression_train(row_ptr, fidx, fval, targets, stream_ptr, nstreams, W, stats, C, eps,
+                               concurrent, stream);
+  if (method < jb::PERCEPTRON || method > jb::NHERD) return (int)hipErrorInvalidValue;
+  if (method >= jb::CW && P == nullptr) return (int)hipErrorInvalidValue;
+  if (nstreams <= 0) return 0;
+  const int threads = 256, blocks = (nstreams * 64 + threads - 1) / threads;
+#define JB_REG_LAUNCH(M)                                                                            \
+  case M:                                                                                           \
+    if (concurrent)                                                                                 \
+      hipLaunchKernelGGL((jb::regression_train_m_kernel<M, true>), dim3(blocks), dim3(threads), 0,  \
+                         stream, row_ptr, fidx, fval, targets, stream_ptr, nstreams, W, P, stats,   \
+                         slot_scratch, C, eps);                                                     \
+    else                                                                                            \
+      hipLaunchKernelGGL((jb::regression_train_m_kernel<M, false>), dim3(blocks), dim3(threads), 0, \
+                         stream, row_ptr, fidx, fval, targets, stream_ptr, nstreams, W, P, stats,   \
+                         slot_scratch, C, eps);                                                     \
+    break;
+  switch (method) {
+    JB_REG_LAUNCH(jb::PERCEPTRON)
+    JB_REG_LAUNCH(jb::PA1)
+    JB_REG_LAUNCH(jb::PA2)
+    JB_REG_LAUNCH(jb::CW)
+    JB_REG_LAUNCH(jb::AROW)
+    JB_REG_LAUNCH(jb::NHERD)
+  }
+#undef JB_REG_LAUNCH
   return (int)hipGetLastError();
 }
 

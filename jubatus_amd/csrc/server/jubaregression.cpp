@@ -1,9 +1,14 @@
-// jubaregression, native: the PA regression server without Python.
+// jubaregression, native: the regression server without Python (methods PA,
+// PA1, PA2, perceptron, CW, AROW, NHERD).
 //
 // Reference: jubatus/server/server/regression_serv.cpp (train :95-130,
 // estimate :132-148, clear), regression_impl.cpp (RPC table) over
-// jubatus_core's PA regression; the update rule and its oracle are in
-// models/regression.py, the kernels in csrc/hip/regression.hip.
+// jubatus_core's PA regression; the update rules and their oracle are in
+// models/regression.py, the kernels in csrc/hip/regression.hip. The reference
+// has PA only: the other six rules are this project's own (the classifier's
+// formulas with one label and 1 - margin replaced by the loss), and parity
+// with later Jubatus releases is unpinned. CW / AROW / NHERD own a precision
+// table P beside w; it is saved, loaded and MIXed (mean) with w.
 //
 // Scope: standalone and distributed servers (linear and push mixers over the
 // native MIX plane, csrc/native/jb_mix_group.hpp), fixed-slot converters and
@@ -48,6 +53,11 @@ extern "C" int jb_regression_train(const int64_t* row_ptr, const int32_t* fidx, 
                                    const float* targets, const int64_t* stream_ptr, int nstreams,
                                    float* W, float* stats, float C, float eps, int concurrent,
                                    hipStream_t stream);
+extern "C" int jb_regression_train_m(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
+                                     const float* targets, const int64_t* stream_ptr, int nstreams,
+                                     float* W, float* P, float* stats, float* slot_scratch,
+                                     int method, float C, float eps, int concurrent,
+                                     hipStream_t stream);
 extern "C" int jb_regression_estimate(const int64_t* row_ptr, const int32_t* fidx,
                                       const float* fval, int n, const float* W, float* out,
                                       hipStream_t stream);
@@ -56,15 +66,21 @@ namespace {
 
 using namespace jb::srv;
 
+// models/linear_oracle.py METHOD_IDS
+const char* const kMethods[7] = {"perceptron", "PA", "PA1", "PA2", "CW", "AROW", "NHERD"};
+
 struct Config {
   std::string text;
-  float eps = 0.1f, C = 3.40282e+38f;
+  std::string method = "PA";
+  int mid = 1;           // index in kMethods
+  bool cov = false;      // CW / AROW / NHERD: the precision table P
+  float eps = 0.1f, C = 3.40282e+38f;   // C: the learning rate for perceptron
   Rules rules;
   bool wide = false;     // the wide rule set on the host (bigram / combinations)
   WideRules wrules;
 };
 
-// models/regression.py PARegression.__init__ + the fixed-slot converter check
+// models/regression.py Regression.__init__ + the fixed-slot converter check
 bool parse_config(const std::string& text, Config* c, std::string* why) {
   Value v;
   try {
@@ -74,8 +90,18 @@ bool parse_config(const std::string& text, Config* c, std::string* why) {
     return false;
   }
   if (v.kind != Value::MAP) { *why = "configuration must be a JSON object"; return false; }
-  if (v.str_or("method", "") != "PA") { *why = "method " + v.str_or("method", "") + " is not PA"; return false; }
-  if (const Value* p = v.get("parameter")) {
+  c->method = v.str_or("method", "");
+  c->mid = -1;
+  for (int k = 0; k < 7; ++k)
+    if (c->method == kMethods[k]) c->mid = k;
+  if (c->mid < 0) {
+    *why = "method " + c->method + " is not PA, PA1, PA2, perceptron, CW, AROW or NHERD";
+    return false;
+  }
+  c->cov = c->mid >= 4;
+  const Value* p = v.get("parameter");
+  const Value* lr = nullptr;
+  if (p) {
     if (const Value* s = p->get("sensitivity")) {
       if (!s->is_num()) { *why = "sensitivity"; return false; }
       c->eps = (float)s->num();
@@ -83,9 +109,24 @@ bool parse_config(const std::string& text, Config* c, std::string* why) {
     if (const Value* r = p->get("regularization_weight")) {
       if (!r->is_num()) { *why = "regularization_weight"; return false; }
       c->C = (float)r->num();
+    } else if (c->cov) {
+      *why = c->method + " requires parameter regularization_weight";
+      return false;
     }
+    lr = p->get("learning_rate");
+  } else if (c->cov) {
+    *why = c->method + " requires parameter regularization_weight";
+    return false;
   }
   if (c->eps < 0 || !(c->C > 0)) { *why = "sensitivity must be >= 0 and regularization_weight > 0"; return false; }
+  if (c->method == "perceptron") {
+    c->C = 1.0f;
+    if (lr) {
+      if (!lr->is_num()) { *why = "learning_rate"; return false; }
+      c->C = (float)lr->num();
+    }
+    if (!(c->C > 0)) { *why = "learning_rate must be > 0"; return false; }
+  }
   const Value* conv = v.get("converter");
   Value empty;
   empty.kind = Value::MAP;
@@ -129,6 +170,9 @@ class Regression : public jb::mix::Mixable {
     conv_.configure(r, cfg.wide, cfg.wrules);
     if (w_) HIPCHK(hipFree(w_));
     if (stats_) HIPCHK(hipFree(stats_));
+    if (p_) HIPCHK(hipFree(p_));
+    p_ = nullptr;
+    if (cfg.cov) HIPCHK(hipMalloc((void**)&p_, r.H * 4));
     HIPCHK(hipMalloc((void**)&w_, r.H * 4));
     HIPCHK(hipMalloc((void**)&stats_, 3 * 4));
     clear_locked();
@@ -162,8 +206,17 @@ class Regression : public jb::mix::Mixable {
     upload(n, slots);
     HIPCHK(hipMemcpyAsync(d_tgt_.get(n), tgt_.p, 4 * (size_t)n, hipMemcpyHostToDevice, stream_));
     HIPCHK(hipMemcpyAsync(d_sp_.get(sp.size()), sp.data(), 8 * sp.size(), hipMemcpyHostToDevice, stream_));
-    const int rc = jb_regression_train(d_row_.p, d_idx_.p, d_val_.p, d_tgt_.p, d_sp_.p, ns, w_, stats_,
-                                       cfg_.C, cfg_.eps, ns > 1 ? 1 : 0, stream_);
+    int rc;
+    if (cfg_.method == "PA") {
+      rc = jb_regression_train(d_row_.p, d_idx_.p, d_val_.p, d_tgt_.p, d_sp_.p, ns, w_, stats_, cfg_.C,
+                               cfg_.eps, ns > 1 ? 1 : 0, stream_);
+    } else {
+      // d_scratch_: one float per slot, where the kernel parks the P
+      // increments of samples wider than its register slots
+      float* scratch = cfg_.cov ? d_scratch_.get(std::max<int64_t>(slots, 1)) : nullptr;
+      rc = jb_regression_train_m(d_row_.p, d_idx_.p, d_val_.p, d_tgt_.p, d_sp_.p, ns, w_, p_, stats_, scratch,
+                                 cfg_.mid, cfg_.C, cfg_.eps, ns > 1 ? 1 : 0, stream_);
+    }
     if (rc != 0) throw std::runtime_error("jb_regression_train failed: " + std::to_string(rc));
     HIPCHK(hipStreamSynchronize(stream_));
     samples_ += (uint64_t)n;
@@ -246,29 +299,33 @@ class Regression : public jb::mix::Mixable {
   uint64_t mix(jb::mix::Group& grp) override {
     jb::mix::Star& star = grp.star();
     jb::mix::Plane& pl = grp.plane();
-    uint64_t gen, H;
+    uint64_t gen, H, T;
     {
       std::lock_guard<std::mutex> g(mu_);
       gen = gen_;
       H = cfg_.rules.H;
-      // snapshot (behind the queued training): [w | stats] -> snap, red
-      if (jb_mix_gather(w_, nullptr, 1, nullptr, (int64_t)H, map_.p, 1, snap_.get(H + 3), stream_) != 0)
+      T = table_floats();
+      // snapshot (behind the queued training): [w | P | stats] -> snap, red
+      // (w and P row by row, as jb_mix_gather lays W and S out)
+      if (jb_mix_gather(w_, p_, 1, nullptr, (int64_t)H, map_.p, 1, snap_.get(T + 3), stream_) != 0)
         throw std::runtime_error("jb_mix_gather failed");
-      HIPCHK(hipMemcpyAsync(snap_.p + H, stats_, 12, hipMemcpyDeviceToDevice, stream_));
-      HIPCHK(hipMemcpyAsync(red_.get(H + 3), snap_.p, (H + 3) * 4, hipMemcpyDeviceToDevice, stream_));
+      HIPCHK(hipMemcpyAsync(snap_.p + T, stats_, 12, hipMemcpyDeviceToDevice, stream_));
+      HIPCHK(hipMemcpyAsync(red_.get(T + 3), snap_.p, (T + 3) * 4, hipMemcpyDeviceToDevice, stream_));
       HIPCHK(hipEventRecord(mix_ev_, stream_));
       HIPCHK(hipStreamWaitEvent(mixs_, mix_ev_, 0));
     }
     // every member checks the layout (a different table height cannot mix),
     // and a member whose tables were replaced since its snapshot makes the
     // whole group skip the fold (slot 2: max of "replaced")
-    int64_t hh[3] = {(int64_t)H, -(int64_t)H, 0};
+    const int64_t mid = cfg_.mid;
+    int64_t hh[5] = {(int64_t)H, -(int64_t)H, 0, mid, -mid};
     {
       std::lock_guard<std::mutex> g(mu_);
       hh[2] = gen != gen_ ? 1 : 0;
     }
-    star.allreduce_max(hh, 3, grp.deadline());
+    star.allreduce_max(hh, 5, grp.deadline());
     if (hh[0] != -hh[1]) throw std::runtime_error("mix: members disagree on hash_max_size");
+    if (hh[3] != -hh[4]) throw std::runtime_error("mix: members disagree on the method");
     uint64_t wbytes = 0;
     if (conv_.global()) {   // the document statistics of idf / bm25 converters
       std::string dm;
@@ -285,27 +342,27 @@ class Regression : public jb::mix::Mixable {
       last_applied_ = false;
       return 24 + wbytes;
     }
-    pl.allreduce_sum(red_.p, H + 3, grp.deadline());
+    pl.allreduce_sum(red_.p, T + 3, grp.deadline());
     std::lock_guard<std::mutex> g(mu_);
     HIPCHK(hipEventRecord(mix_ev_, mixs_));
     HIPCHK(hipStreamWaitEvent(stream_, mix_ev_, 0));
     if (gen != gen_) {          // cleared / reconfigured / loaded meanwhile: nothing to fold into
       last_applied_ = false;
-      return (H + 3) * 4;
+      return (T + 3) * 4;
     }
     const float inv = 1.f / (float)grp.world();
-    if (jb_mix_fold(w_, nullptr, 1, nullptr, (int64_t)H, map_.p, 1, snap_.p, red_.p, inv, stream_) != 0)
+    if (jb_mix_fold(w_, p_, 1, nullptr, (int64_t)H, map_.p, 1, snap_.p, red_.p, inv, stream_) != 0)
       throw std::runtime_error("jb_mix_fold failed");
     float sn[3], rd[3], cur[3];
-    HIPCHK(hipMemcpyAsync(sn, snap_.p + H, 12, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipMemcpyAsync(rd, red_.p + H, 12, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(sn, snap_.p + T, 12, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(rd, red_.p + T, 12, hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipMemcpyAsync(cur, stats_, 12, hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
     for (int i = 0; i < 3; ++i) cur[i] += rd[i] * inv - sn[i];
     HIPCHK(hipMemcpy(stats_, cur, 12, hipMemcpyHostToDevice));
     last_applied_ = true;
     ++mixes_;
-    return (H + 3) * 4;
+    return (T + 3) * 4;
   }
 
   // push mixers (random / broadcast / skip, push_mixer.cpp:335-408): one
@@ -321,27 +378,29 @@ class Regression : public jb::mix::Mixable {
     jb::mix::Star& star = grp.star();
     jb::mix::Plane& pl = grp.plane();
     const double dl = grp.deadline();
-    uint64_t gen = 0, H = 0;
+    uint64_t gen = 0, H = 0, T = 0;
     if (peer >= 0) {
       std::lock_guard<std::mutex> g(mu_);
       gen = gen_;
       H = cfg_.rules.H;
-      if (jb_mix_gather(w_, nullptr, 1, nullptr, (int64_t)H, map_.p, 1, snap_.get(H + 3), stream_) != 0)
+      T = table_floats();
+      if (jb_mix_gather(w_, p_, 1, nullptr, (int64_t)H, map_.p, 1, snap_.get(T + 3), stream_) != 0)
         throw std::runtime_error("jb_mix_gather failed");
-      HIPCHK(hipMemcpyAsync(snap_.p + H, stats_, 12, hipMemcpyDeviceToDevice, stream_));
-      HIPCHK(hipMemcpyAsync(red_.get(H + 3), snap_.p, (H + 3) * 4, hipMemcpyDeviceToDevice, stream_));
+      HIPCHK(hipMemcpyAsync(snap_.p + T, stats_, 12, hipMemcpyDeviceToDevice, stream_));
+      HIPCHK(hipMemcpyAsync(red_.get(T + 3), snap_.p, (T + 3) * 4, hipMemcpyDeviceToDevice, stream_));
       HIPCHK(hipEventRecord(mix_ev_, stream_));
       HIPCHK(hipStreamWaitEvent(mixs_, mix_ev_, 0));
     }
     // the pair checks the layout and whether both can fold; every call below
     // is one of the round's collectives (a rank without a peer sends nothing)
     std::string me;
-    if (peer >= 0) me = std::to_string(H) + (gen != gen_ ? " 1" : " 0");
+    const std::string lay = std::to_string(H) + "/" + cfg_.method;   // table height and method
+    if (peer >= 0) me = lay + (gen != gen_ ? " 1" : " 0");
     const std::string th = pl.exchange_bytes(star, peer, me, dl);
     bool fold = peer >= 0 && gen == gen_;
     if (peer >= 0) {
-      if (th.substr(0, th.find(' ')) != std::to_string(H))
-        throw std::runtime_error("mix: members disagree on hash_max_size");
+      if (th.substr(0, th.find(' ')) != lay)
+        throw std::runtime_error("mix: members disagree on hash_max_size or on the method");
       fold = fold && th.size() > 2 && th.back() == '0';
     }
     uint64_t wbytes = 0;
@@ -359,7 +418,7 @@ class Regression : public jb::mix::Mixable {
         wbytes = dm.size();
       }
     }
-    pl.pair_sum(star, fold ? red_.p : nullptr, fold ? H + 3 : 0, fold ? peer : -1, dl);
+    pl.pair_sum(star, fold ? red_.p : nullptr, fold ? T + 3 : 0, fold ? peer : -1, dl);
     if (!fold) {
       if (peer >= 0) last_applied_ = false;
       return wbytes;
@@ -369,46 +428,51 @@ class Regression : public jb::mix::Mixable {
     HIPCHK(hipStreamWaitEvent(stream_, mix_ev_, 0));
     if (gen != gen_) {
       last_applied_ = false;
-      return (H + 3) * 4 + wbytes;
+      return (T + 3) * 4 + wbytes;
     }
-    if (jb_mix_fold(w_, nullptr, 1, nullptr, (int64_t)H, map_.p, 1, snap_.p, red_.p, 0.5f, stream_) != 0)
+    if (jb_mix_fold(w_, p_, 1, nullptr, (int64_t)H, map_.p, 1, snap_.p, red_.p, 0.5f, stream_) != 0)
       throw std::runtime_error("jb_mix_fold failed");
     float sn[3], rd[3], cur[3];
-    HIPCHK(hipMemcpyAsync(sn, snap_.p + H, 12, hipMemcpyDeviceToHost, stream_));
-    HIPCHK(hipMemcpyAsync(rd, red_.p + H, 12, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(sn, snap_.p + T, 12, hipMemcpyDeviceToHost, stream_));
+    HIPCHK(hipMemcpyAsync(rd, red_.p + T, 12, hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipMemcpyAsync(cur, stats_, 12, hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
     for (int i = 0; i < 3; ++i) cur[i] += rd[i] * 0.5f - sn[i];
     HIPCHK(hipMemcpy(stats_, cur, 12, hipMemcpyHostToDevice));
     last_applied_ = true;
     ++mixes_;
-    return (H + 3) * 4 + wbytes;
+    return (T + 3) * 4 + wbytes;
   }
 
   // obsolete protocol: rank src sends w and stats; apply = take them
   void hand_over(jb::mix::Group& grp, int src, bool apply) override {
     jb::mix::Plane& pl = grp.plane();
-    uint64_t H;
+    uint64_t H, T;
     {
       std::lock_guard<std::mutex> g(mu_);
       H = cfg_.rules.H;
-      if (grp.rank() == src) {
-        HIPCHK(hipMemcpyAsync(red_.get(H + 3), w_, H * 4, hipMemcpyDeviceToDevice, stream_));
-        HIPCHK(hipMemcpyAsync(red_.p + H, stats_, 12, hipMemcpyDeviceToDevice, stream_));
+      T = table_floats();
+      if (grp.rank() == src) {      // [w | P | stats]
+        HIPCHK(hipMemcpyAsync(red_.get(T + 3), w_, H * 4, hipMemcpyDeviceToDevice, stream_));
+        if (p_) HIPCHK(hipMemcpyAsync(red_.p + H, p_, H * 4, hipMemcpyDeviceToDevice, stream_));
+        HIPCHK(hipMemcpyAsync(red_.p + T, stats_, 12, hipMemcpyDeviceToDevice, stream_));
       } else {
-        red_.get(H + 3);
+        red_.get(T + 3);
       }
       HIPCHK(hipStreamSynchronize(stream_));
     }
-    int64_t hh[2] = {(int64_t)H, -(int64_t)H};
-    grp.star().allreduce_max(hh, 2, grp.deadline());
+    const int64_t mid = cfg_.mid;
+    int64_t hh[4] = {(int64_t)H, -(int64_t)H, mid, -mid};
+    grp.star().allreduce_max(hh, 4, grp.deadline());
     if (hh[0] != -hh[1]) throw std::runtime_error("hand-over: members disagree on hash_max_size");
-    pl.bcast(red_.p, (H + 3) * 4, src, grp.deadline());
+    if (hh[2] != -hh[3]) throw std::runtime_error("hand-over: members disagree on the method");
+    pl.bcast(red_.p, (T + 3) * 4, src, grp.deadline());
     if (!apply || grp.rank() == src) return;
     std::lock_guard<std::mutex> g(mu_);
     ++gen_;
     HIPCHK(hipMemcpyAsync(w_, red_.p, H * 4, hipMemcpyDeviceToDevice, stream_));
-    HIPCHK(hipMemcpyAsync(stats_, red_.p + H, 12, hipMemcpyDeviceToDevice, stream_));
+    if (p_) HIPCHK(hipMemcpyAsync(p_, red_.p + H, H * 4, hipMemcpyDeviceToDevice, stream_));
+    HIPCHK(hipMemcpyAsync(stats_, red_.p + T, 12, hipMemcpyDeviceToDevice, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
   }
 
@@ -416,20 +480,29 @@ class Regression : public jb::mix::Mixable {
   std::string pack_user_data() {
     std::lock_guard<std::mutex> g(mu_);
     const uint64_t H = cfg_.rules.H;
-    std::vector<float> w(H);
+    std::vector<float> w(H), P;
     float st[3];
     HIPCHK(hipStreamSynchronize(stream_));
     HIPCHK(hipMemcpy(w.data(), w_, H * 4, hipMemcpyDeviceToHost));
+    if (p_) {
+      P.resize(H);
+      HIPCHK(hipMemcpy(P.data(), p_, H * 4, hipMemcpyDeviceToHost));
+    }
     HIPCHK(hipMemcpy(st, stats_, sizeof st, hipMemcpyDeviceToHost));
+    // CW / AROW / NHERD: the rows with w != 0 or P != 1, and "P" over them
     std::vector<int64_t> rows;
-    std::vector<float> vals;
+    std::vector<float> vals, pvals;
     for (uint64_t h = 0; h < H; ++h)
-      if (w[h] != 0.f) { rows.push_back((int64_t)h); vals.push_back(w[h]); }
+      if (w[h] != 0.f || (p_ && P[h] != 1.f)) {
+        rows.push_back((int64_t)h);
+        vals.push_back(w[h]);
+        if (p_) pvals.push_back(P[h]);
+      }
     MsgpackWriter u;
     u.arr(2);
     u.uint(1);
-    u.map(6);
-    u.str("method"); u.str("PA");
+    u.map(p_ ? 7 : 6);
+    u.str("method"); u.str(cfg_.method);
     u.str("H"); u.uint(H);
     u.str("rows"); u.bin(rows.data(), rows.size() * 8);
     u.str("w"); u.bin(vals.data(), vals.size() * 4);
@@ -437,6 +510,7 @@ class Regression : public jb::mix::Mixable {
     for (float x : st) u.dbl((double)x);
     u.str("weights");
     conv_.pack(u);
+    if (p_) { u.str("P"); u.bin(pvals.data(), pvals.size() * 4); }
     return std::move(u.out);
   }
 
@@ -449,18 +523,27 @@ class Regression : public jb::mix::Mixable {
       throw std::runtime_error("model hash_max_size differs from the configuration");
     if (!rv || !wv || rv->s.size() / 8 != wv->s.size() / 4 || !sv || sv->kind != Value::ARR || sv->a.size() != 3)
       throw std::runtime_error("broken model data: regression tables");
+    const Value* mv = obj.get("method");
+    if (mv && mv->is_str() && mv->s != cfg_.method)
+      throw std::runtime_error("model method " + mv->s + " differs from the configured " + cfg_.method);
+    const Value* pv = obj.get("P");      // absent: the initial precision
+    if (pv && pv->s.size() / 4 != rv->s.size() / 8)
+      throw std::runtime_error("broken model data: regression tables");
     std::lock_guard<std::mutex> g(mu_);
     ++gen_;
     const uint64_t Hn = cfg_.rules.H;
-    std::vector<float> w(Hn, 0.f);
+    std::vector<float> w(Hn, 0.f), P(p_ ? Hn : 0, 1.f);
     const int64_t* rows = (const int64_t*)rv->s.data();
     const float* vals = (const float*)wv->s.data();
+    const float* pvals = pv ? (const float*)pv->s.data() : nullptr;
     for (size_t k = 0; k < rv->s.size() / 8; ++k) {
       if (rows[k] < 0 || (uint64_t)rows[k] >= Hn) throw std::runtime_error("broken model data: row index");
       w[rows[k]] = vals[k];
+      if (p_ && pvals) P[rows[k]] = pvals[k];
     }
     float st[3] = {(float)sv->a[0].num(), (float)sv->a[1].num(), (float)sv->a[2].num()};
     HIPCHK(hipStreamSynchronize(stream_));
+    if (p_) HIPCHK(hipMemcpy(p_, P.data(), Hn * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(w_, w.data(), Hn * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(stats_, st, sizeof st, hipMemcpyHostToDevice));
     conv_.unpack(obj.get("weights"));
@@ -469,7 +552,7 @@ class Regression : public jb::mix::Mixable {
   void status(std::vector<std::pair<std::string, std::string>>* st) {
     auto add = [&](const char* k, const std::string& v) { st->emplace_back(k, v); };
     add("num_features", std::to_string(cfg_.rules.H));
-    add("method", "PA");
+    add("method", cfg_.method);
     add("storage", "hbm");
     add("fv_path", "gpu");
     add("server_runtime", "native");
@@ -490,7 +573,14 @@ class Regression : public jb::mix::Mixable {
     HIPCHK(hipMemsetAsync(w_, 0, cfg_.rules.H * 4, stream_));
     HIPCHK(hipMemsetAsync(stats_, 0, 3 * 4, stream_));
     HIPCHK(hipStreamSynchronize(stream_));
+    if (p_) {                      // the initial precision
+      const std::vector<float> ones(cfg_.rules.H, 1.f);
+      HIPCHK(hipMemcpy(p_, ones.data(), cfg_.rules.H * 4, hipMemcpyHostToDevice));
+    }
   }
+
+  // floats of the model tables in a MIX buffer: w, and P for the confidence methods
+  uint64_t table_floats() const { return cfg_.rules.H * (p_ ? 2 : 1); }
 
   // one list<[score, datum]> body appended to the host CSR (validated as a
   // whole: false leaves nothing behind)
@@ -555,6 +645,7 @@ class Regression : public jb::mix::Mixable {
   DevBuf<float> snap_, red_;
   DevBuf<int32_t> map_;
   float* w_ = nullptr;
+  float* p_ = nullptr;      // precision table of CW / AROW / NHERD, else null
   float* stats_ = nullptr;
   uint64_t samples_ = 0;
   LinearConv conv_;
@@ -563,7 +654,7 @@ class Regression : public jb::mix::Mixable {
   HostVec<int64_t> row_;
   DevBuf<int64_t> d_row_, d_sp_;
   DevBuf<int32_t> d_idx_;
-  DevBuf<float> d_val_, d_tgt_, d_out_;
+  DevBuf<float> d_val_, d_scratch_, d_tgt_, d_out_;
 };
 
 class Server {

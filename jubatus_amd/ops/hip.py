@@ -61,6 +61,9 @@ _SIGS = {
     "jb_scale": [_c_void_p, _i64, _f32, _c_void_p],
     "jb_regression_train": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
                             _c_void_p, _c_void_p, _f32, _f32, _i32, _c_void_p],
+    "jb_regression_train_m": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
+                              _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _f32, _f32, _i32,
+                              _c_void_p],
     "jb_regression_estimate": [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
                                _c_void_p],
     "jb_signature": [_c_void_p, _c_void_p, _c_void_p, _i32, _i32, _u64, _i32, _c_void_p,
@@ -907,12 +910,44 @@ def scale_(t: torch.Tensor, a: float) -> None:
 
 
 def regression_train(row_ptr, fidx, fval, targets, stream_ptr, nstreams: int, W, stats,
-                     C: float, eps: float, concurrent: bool) -> None:
+                     C: float, eps: float, concurrent: bool, method: str = "PA", P=None,
+                     slot_scratch=None) -> None:
+    """one launch of csrc/hip/regression.hip. ``method``: a key of
+    linear_oracle.METHOD_IDS; ``C`` is the learning rate for perceptron. CW,
+    AROW and NHERD take the precision table ``P`` (like W) and, for samples of
+    more than 256 slots, ``slot_scratch`` (float32, as long as fval; without
+    it the widths are checked here, which costs a device synchronisation).
+    PA takes the entry it always took."""
     _dev(W, torch.float32, "W")
     _dev(stats, torch.float32, "stats")
     _dev(targets, torch.float32, "targets")
     if W.dim() != 1 or stats.numel() < 3 or stream_ptr.numel() < nstreams + 1:
         raise ValueError("regression_train: bad operand shapes")
+    if method != "PA":
+        from ..models.linear_oracle import METHOD_IDS, USES_COVARIANCE
+        if method not in METHOD_IDS:
+            raise ValueError(f"regression_train: unknown method {method}")
+        mid = METHOD_IDS[method]
+        if mid in USES_COVARIANCE:
+            if P is None:
+                raise ValueError(f"regression_train: {method} needs the precision table P")
+            _dev(P, torch.float32, "P")
+            if P.shape != W.shape:
+                raise ValueError("regression_train: P must have the shape of W")
+            if slot_scratch is not None:
+                _dev(slot_scratch, torch.float32, "slot_scratch")
+                if slot_scratch.numel() < fval.numel():
+                    raise ValueError("regression_train: slot_scratch is shorter than fval")
+            elif row_ptr.numel() > 1 and int((row_ptr[1:] - row_ptr[:-1]).max()) > 256:
+                raise ValueError("regression_train: samples of more than 256 slots need slot_scratch")
+        else:
+            P = slot_scratch = None
+        rc = _fn("jb_regression_train_m")(_p(row_ptr), _p(fidx), _p(fval), _p(targets),
+                                          _p(stream_ptr), nstreams, _p(W), _p(P), _p(stats),
+                                          _p(slot_scratch), mid, float(C), float(eps),
+                                          1 if concurrent else 0, _stream())
+        _check(rc, "jb_regression_train_m")
+        return
     rc = _fn("jb_regression_train")(_p(row_ptr), _p(fidx), _p(fval), _p(targets), _p(stream_ptr),
                                     nstreams, _p(W), _p(stats), float(C), float(eps),
                                     1 if concurrent else 0, _stream())

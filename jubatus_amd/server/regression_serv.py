@@ -9,18 +9,18 @@ from ..common.exceptions import ArgumentError
 from ..common.mprpc import split_params
 from ..framework.engine_serv import EngineServ
 from ..fv_converter.converter import DatumToFvConverter, device_hash_max_size
-from ..models.regression import PARegression
+from ..models.regression import Regression
 
 
 class RegressionServ(EngineServ):
     type_name = "regression"
 
     def build_driver(self, cfg: dict):
-        return PARegression(cfg.get("method"), cfg.get("parameter"),
-                            DatumToFvConverter(cfg.get("converter") or {},
-                                               default_hash_max_size=(device_hash_max_size()
-                                                                      if self.device is not None else None)),
-                            device=self.device)
+        return Regression(cfg.get("method"), cfg.get("parameter"),
+                          DatumToFvConverter(cfg.get("converter") or {},
+                                             default_hash_max_size=(device_hash_max_size()
+                                                                    if self.device is not None else None)),
+                          device=self.device)
 
     def train(self, data) -> int:
         self.check_set_config()

@@ -67,6 +67,33 @@ class RowEngine:
         f = self.conv.convert_and_update_weight(d) if update_weight else self.conv.convert(d)
         return self.conv.hashed(f)
 
+    def fvs_of(self, ds: list) -> list:
+        """hashed feature vectors of many query datums -> [(idx, val)]: one
+        native hashing pass when the converter allows it (the vectors are
+        slices of its CSR and may hold idx < 0, which every index skips), the
+        Python converter otherwise. Never updates the weights."""
+        h = self._hasher() if len(ds) > 1 else None
+        if h is None:
+            return [self.fv_of(d) for d in ds]
+        import msgpack
+        import numpy as np
+        body = msgpack.packb([d.to_msgpack() for d in ds], use_bin_type=False)
+        n = len(ds)
+        cap = max(1024, 64 * n)
+        while True:
+            idx = np.empty(cap, np.int32)
+            val = np.empty(cap, np.float32)
+            rp = np.zeros(n + 1, np.int64)
+            got, _, err = h.hash([body], idx.ctypes.data, val.ctypes.data, rp.ctypes.data, n, cap,
+                                 False)
+            if err == 2:
+                cap *= 4
+                continue
+            if err or got != n:
+                return [self.fv_of(d) for d in ds]
+            break
+        return [(idx[rp[i]:rp[i + 1]], val[rp[i]:rp[i + 1]]) for i in range(n)]
+
     def _set(self, rid: str, dicts, bump: bool = True, update_weight: bool = True) -> None:
         if self.gpu and hasattr(self.index, "set_rows_direct") and \
                 self._set_direct(rid, dicts, bump, update_weight):

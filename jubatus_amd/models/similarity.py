@@ -295,6 +295,23 @@ class LshIndex:
                               self.similarity_of if similar else None)
         return topk(self.distances(rows, nrows), k, self.similarity_of if similar else None)
 
+    def query_device(self, rows: list, nrows: int, k: int):
+        """as query(), but the lists stay on the device: -> (dist float32
+        [nq, kk], row int32 [nq, kk]) ascending, +inf padded (kk = k on the
+        fused top-k, min(k, nrows) past TOPK_MAX_K). GPU index, nrows > 0,
+        k > 0 and at least one query."""
+        if not (self.gpu and nrows > 0 and k > 0 and rows):
+            raise ValueError("query_device: needs a device index, rows, queries and k > 0")
+        import torch
+        from ..ops import hip
+        if k <= hip.TOPK_MAX_K and self.words <= hip.TOPK_MAX_WORDS:
+            qb, qn = self._signatures(rows)
+            return hip.topk_hamming(qb.contiguous(), qn.contiguous(), len(rows), self.bits,
+                                    self.norms, self.valid, nrows, self.hash_num, self.metric, k)
+        d, i = torch.topk(self.distances(rows, nrows), min(k, nrows), dim=1, largest=False,
+                          sorted=True)
+        return d.contiguous(), i.to(torch.int32).contiguous()
+
     def query_direct(self, idx, val, row_ptr, nq: int, nrows: int, k: int,
                      similar: bool) -> list[list[tuple[int, float]]] | None:
         """latency path: host-hashed query CSR (numpy int32 / float32 / int64)
@@ -797,6 +814,42 @@ class InvertedIndex:
         if similar:
             out = [[(j, float(-dd if self.euclid else 1.0 - dd)) for j, dd in r] for r in out]
         return out
+
+    def _topk_device(self, sc, nq: int, nrows: int, k: int):
+        import torch
+        from ..ops import hip
+        if k <= hip.TOPK_MAX_K:
+            return hip.topk_scores(sc, nq, nrows, k, flip=not self.euclid)
+        m = sc.view(nq, nrows)      # wider than the fused top-k: torch.topk on the score matrix
+        dist = m if self.euclid else (1.0 - m).nan_to_num(posinf=math.inf)
+        d, i = torch.topk(dist, min(k, nrows), dim=1, largest=False, sorted=True)
+        return d.contiguous(), i.to(torch.int32).contiguous()
+
+    def query_device(self, rows: list, nrows: int, k: int):
+        """as query(), but the lists stay on the device: -> (dist float32
+        [nq, kk], row int32 [nq, kk]) ascending in the distance view (1 -
+        cosine / euclid), +inf padded (kk = k on the fused top-k, min(k, nrows)
+        past TOPK_MAX_K). POOL_MAX_Q queries per pass over the pool. GPU index,
+        nrows > 0, k > 0 and at least one query."""
+        if not (self.gpu and nrows > 0 and k > 0 and rows):
+            raise ValueError("query_device: needs a device index, rows, queries and k > 0")
+        import torch
+        from ..ops import hip
+        ds, rs = [], []
+        for b0 in range(0, len(rows), hip.POOL_MAX_Q):
+            b1 = min(len(rows), b0 + hip.POOL_MAX_Q)
+            q = self._queries_device(rows[b0:b1])
+            if q[-1] > hip.POOL_MAX_Q_ENTRIES and b1 - b0 > 1:     # one query at a time
+                parts = [(self._queries_device(rows[j:j + 1]), 1) for j in range(b0, b1)]
+            else:
+                parts = [(q, b1 - b0)]
+            for qq, n in parts:
+                d, i = self._topk_device(self._scan(qq, n, nrows), n, nrows, k)
+                ds.append(d)
+                rs.append(i)
+        if len(ds) == 1:
+            return ds[0], rs[0]
+        return torch.cat(ds), torch.cat(rs)
 
     def scores_device(self, row, nrows: int):
         """device score vector (cosine similarity / euclidean distance)"""

@@ -8,6 +8,7 @@ order naturally with torch ops and RCCL collectives.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import time
 
@@ -77,6 +78,8 @@ _SIGS = {
                            _c_void_p, _c_void_p],
     "jb_topk": [_i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _i32,
                 _i32, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "jb_nn_reduce": [_c_void_p, _c_void_p, _i32, _i32, _c_void_p, _i32, _i32, _f32, _c_void_p,
+                     _c_void_p, _c_void_p],
     "jb_topk_blocks": [_i64, _i32],
     "jb_topk_mq_stats": [_c_void_p],
     "jb_topk_direct_scratch": [_i32],
@@ -400,6 +403,31 @@ def _topk(mode, qbits, qnorm, nq, tbits, tnorm, valid, nrows, words, hash_num, m
                         _p(out_i), _stream())
     _check(rc, "jb_topk")
     return out_d, out_i
+
+
+NN_REDUCE_MODES = {"uniform": 0, "distance": 1, "similarity": 2}
+
+
+def nn_reduce(dist, row, nq: int, k: int, targets, nrows: int, mode: int, alpha: float):
+    """Weighted mean of the neighbours' targets (csrc/hip/nn_reduce.hip) over
+    the [nq, k] lists of topk_hamming / topk_scores (or a torch.topk of the
+    same layout, any k): -> (out float32 [nq], out_n int32 [nq]). ``mode``: a
+    value of NN_REDUCE_MODES; ``alpha`` is read by mode 1 only."""
+    _dev(dist, torch.float32, "dist")
+    _dev(row, torch.int32, "row")
+    _dev(targets, torch.float32, "targets")
+    if mode not in (0, 1, 2) or not 0.0 <= float(alpha) < math.inf:
+        raise ValueError("nn_reduce: mode or alpha out of range")
+    if nq < 0 or k < 0 or nrows < 0:
+        raise ValueError("nn_reduce: negative size")
+    if dist.numel() < nq * k or row.numel() < nq * k or targets.numel() < nrows:
+        raise ValueError("nn_reduce: bad operand shapes")
+    out = torch.empty(nq, dtype=torch.float32, device=dist.device)
+    out_n = torch.empty(nq, dtype=torch.int32, device=dist.device)
+    rc = _fn("jb_nn_reduce")(_p(dist), _p(row), nq, k, _p(targets), nrows, mode, float(alpha),
+                             _p(out), _p(out_n), _stream())
+    _check(rc, "jb_nn_reduce")
+    return out, out_n
 
 
 def sparse_scan(qidx, qval, qnorm2: float, row_ptr, ridx, rval, rnorm2, valid, nrows: int,

@@ -72,17 +72,32 @@ __device__ __forceinline__ uint32_t byte_fast(const uint8_t* q, int p, int lim) 
 }
 
 // (arity - 1) of the token at p, the only quantity the depth scan needs:
-// containers give their element count - 1, everything else -1
+// containers give their element count - 1, everything else -1.
+//
+// The count of a 16 / 32-bit container header is clamped to kScanBytes, so
+// that the depth sums cannot overflow an int: a staged request has fewer than
+// kScanBytes tokens, at most kScanBytes / 3 of them such headers, each adding
+// less than 2 * kScanBytes, so every partial sum lies in
+// (-kScanBytes, kScanBytes * kScanBytes) - inside int. A request with a
+// clamped container is still rejected: that token adds at least
+// kScanBytes - 1, the header takes 3 bytes or more, so the other tokens
+// after position 0 number at most len - 4 <= kScanBytes - 4 and each adds
+// -1 or more; the total is therefore >= 3 > 0 >= -nsamples and the
+// `total != -nsamples` test fires (the real count is unsatisfiable too: no
+// body of len bytes holds kScanBytes elements). For the sample starts, a
+// write to s_start[-h] needs h < mn <= 1, i.e. -h >= 0, and is guarded by
+// -h < nsamples; without overflow h is the true partial sum, so -h stays in
+// [0, nsamples).
 __device__ __forceinline__ int token_d(const uint8_t* q, int p, int lim) {
   const uint32_t t = byte_fast(q, p, lim);
   if ((t & 0xe0) == 0x80) return (t <= 0x8f ? 2 * (int)(t & 0x0f) : (int)(t & 0x0f)) - 1;
   if (t < 0xdc || t > 0xdf) return -1;
   const uint32_t b1 = byte_fast(q, p + 1, lim), b2 = byte_fast(q, p + 2, lim);
-  if (t == 0xdc) return (int)((b1 << 8) | b2) - 1;
-  if (t == 0xde) return 2 * (int)((b1 << 8) | b2) - 1;
-  uint32_t n = (b1 << 24) | (b2 << 16) | (byte_fast(q, p + 3, lim) << 8) | byte_fast(q, p + 4, lim);
-  if (n > 0x3fffffffu) n = 0x3fffffffu;
-  return (t == 0xdd ? (int)n : 2 * (int)n) - 1;
+  uint32_t n = (b1 << 8) | b2;
+  if (t == 0xdd || t == 0xdf)
+    n = (b1 << 24) | (b2 << 16) | (byte_fast(q, p + 3, lim) << 8) | byte_fast(q, p + 4, lim);
+  if (n > (uint32_t)kScanBytes) n = (uint32_t)kScanBytes;
+  return ((t & 2) ? 2 * (int)n : (int)n) - 1;   // 0xde / 0xdf: maps
 }
 
 // size of the token at p (containers: header only), unchecked reads

@@ -301,7 +301,7 @@ class FeaturePipeline:
         self._glast = None              # (set, R, n, slot_cap) of the last batch, if the GPU scan took it
         self.set_wait_s = 0.0           # host time waiting for a device set to come free
 
-        self._ltab = None                 # (label version, device hash, meta, blob)
+        self._ltab = None                 # (label table, its version, device hash, meta, blob)
         if self.fast:
             rt = GpuRuleTable(converter)
             self.rules = rt
@@ -378,12 +378,15 @@ class FeaturePipeline:
         return self._launch(pin, arena.buf, n, nbytes, nslots, R, labeled)
 
     def label_table(self, table) -> tuple:
+        # keyed on the table as well as its version: two tables that have seen
+        # the same number of changes hold different labels. The cached tuple
+        # keeps the table alive, so its identity cannot pass to another object.
         v = table.version()
-        if self._ltab is None or self._ltab[0] != v:
+        if self._ltab is None or self._ltab[0] is not table or self._ltab[1] != v:
             th, tm, blob = label_table_arrays(table.names(), table.alive())
-            self._ltab = (v, torch.from_numpy(th).to(self.device),
+            self._ltab = (table, v, torch.from_numpy(th).to(self.device),
                           torch.from_numpy(tm).to(self.device), torch.from_numpy(blob).to(self.device))
-        return self._ltab[1:]
+        return self._ltab[2:]
 
     def scan_batch_args(self, arena: RequestArena, offs: np.ndarray, lens: np.ndarray, table,
                         check: ScanCheck, counts: np.ndarray | None = None):

@@ -1,4 +1,4 @@
-"""Online clustering over compressive coresets: k-means and GMM.
+"""Online clustering over compressive coresets: k-means, GMM and DBSCAN.
 
 Reference: jubatus/server/server/clustering_serv.cpp:71-151 (push,
 get_revision, get_core_members, get_k_center, get_nearest_center,
@@ -19,7 +19,13 @@ Pipeline (our design, documented):
   a new coreset decays older weights by exp(-forgetting_factor) and drops
   points whose weight falls below ``forgetting_threshold``;
 * clustering: weighted k-means (k-means++ seeding from ``seed``, Lloyd
-  iterations) or a diagonal-covariance GMM (EM initialised from k-means).
+  iterations), a diagonal-covariance GMM (EM initialised from k-means), or
+  DBSCAN over the weighted coreset points (``eps``, ``min_core_point``; no k,
+  outliers stay noise). The reference release has no dbscan: its
+  order-independent definition here is this project's own, parity with later
+  Jubatus releases unpinned (docs/clustering_dbscan.md); on a device the
+  density graph is built by csrc/hip/dbscan.hip, without one by the float64
+  host path ``dbscan_host`` below.
 
 Storage (MI355X design): points never live as per-point Python objects. A
 push is converted in ONE native call (csrc/native/jb_hostfv_wide.hpp
@@ -57,6 +63,52 @@ KEY_SPACE = (1 << 31) - 1      # feature keys: hashed names (int32)
 class NotPerformed(RuntimeError):
     def __init__(self):
         super().__init__("clustering is not performed yet")
+
+
+class NotSupported(RuntimeError):
+    """a query the configured method cannot answer (dbscan has no centers)"""
+
+    def __init__(self, query: str, method: str):
+        super().__init__(f"{query} is not supported by {method}")
+
+
+def dbscan_host(X: np.ndarray, w: np.ndarray, eps: float, min_core_point: float):
+    """the five DBSCAN rules of docs/clustering_dbscan.md in float64 ->
+    (label int64 [n]: smallest point index of the cluster, -1 noise; mass [n])"""
+    X = np.asarray(X, np.float64)
+    w = np.asarray(w, np.float64)
+    n = X.shape[0]
+    xn = (X * X).sum(1)
+    A = np.empty((n, n), dtype=bool)
+    for a in range(0, n, 1024):                      # row blocks: no n x n float64
+        b = min(n, a + 1024)
+        d2 = np.maximum((xn[a:b, None] + xn[None, :]) - 2.0 * (X[a:b] @ X.T), 0.0)
+        A[a:b] = d2 <= eps * eps
+    A |= A.T                                         # the blocked products may round (i, j) and (j, i) apart
+    A[np.arange(n), np.arange(n)] = True
+    mass = A @ w
+    core = mass >= min_core_point
+    label = np.full(n, -1, np.int64)
+    ci = np.flatnonzero(core)
+    Ac = A[np.ix_(ci, ci)]
+    seen = np.zeros(ci.size, dtype=bool)
+    for s in range(ci.size):                         # ascending: s is its component's minimum
+        if seen[s]:
+            continue
+        front = np.zeros(ci.size, dtype=bool)
+        front[s] = True
+        seen[s] = True
+        while front.any():
+            front = Ac[front].any(0) & ~seen
+            seen |= front
+            label[ci[front]] = ci[s]
+        label[ci[s]] = ci[s]
+    bi = np.flatnonzero(~core)
+    if bi.size and ci.size:
+        big = np.iinfo(np.int64).max
+        best = np.where(A[np.ix_(bi, ci)], label[ci][None, :], big).min(1)
+        label[bi] = np.where(best == big, -1, best)
+    return label, mass
 
 
 def _ranges(starts: np.ndarray, lens: np.ndarray) -> np.ndarray:
@@ -139,7 +191,7 @@ class PointSet:
 class Clustering:
     def __init__(self, method: str, parameter: dict | None, converter: DatumToFvConverter,
                  device: Any = None):
-        if method not in ("kmeans", "gmm"):
+        if method not in ("kmeans", "gmm", "dbscan"):
             raise ValueError(f"unsupported clustering method: {method}")
         p = dict(parameter or {})
         self.method = method
@@ -147,6 +199,17 @@ class Clustering:
         self.compressor = p.get("compressor_method", "simple")
         if self.compressor not in COMPRESSORS:
             raise ValueError(f"unknown compressor_method: {self.compressor}")
+        self.eps = self.min_core_point = None
+        if method == "dbscan":
+            for name in ("eps", "min_core_point"):
+                v = p.get(name)
+                if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 < v < math.inf:
+                    raise ValueError(f"dbscan: {name} is required and must be a positive number")
+                setattr(self, name, float(v))
+            if self.compressor != "simple":
+                # k-means++ representatives would move mass between neighbourhoods
+                raise ValueError("dbscan: compressor_method must be simple")
+            self.k = max(self.k, 1)                 # ignored by dbscan: never a reason to refuse
         self.bucket_size = int(p.get("bucket_size", 1000))
         self.compressed = int(p.get("compressed_bucket_size", 100))
         self.bicriteria = int(p.get("bicriteria_base_size", 10))
@@ -194,6 +257,9 @@ class Clustering:
             self._dim_keys = np.zeros(0, np.int64)
             self.assign: list[int] = []
             self.core = PointSet.empty(self._names)
+            self._performed = False
+            self.n_clusters = 0     # dbscan: clusters and noise points of the last run
+            self.n_noise = 0
             self._rng = random.Random(self.seed)
 
     # ------------------------------------------------------------ tensors
@@ -376,7 +442,36 @@ class Clustering:
     def _all_core(self) -> PointSet:
         return PointSet.concat(self.buckets + [self.others], self._names)
 
+    def _recluster_dbscan(self) -> None:
+        pts = self._all_core()
+        n = len(pts)
+        if n == 0:
+            return
+        keys, dims = self._columns(pts)
+        label = None
+        if self.gpu and keys.size >= 1:
+            from ..ops import hip
+            if n <= hip.DBSCAN_MAX_N:
+                torch = self._t()
+                X = self._dense_keys(pts, keys, self.device)
+                w = torch.tensor(pts.w, dtype=torch.float32, device=X.device)
+                label = hip.dbscan(X.contiguous(), w, self.eps, self.min_core_point)[0].cpu().numpy()
+        if label is None:
+            X = self._dense_keys(pts, keys, "cpu").numpy()
+            label = dbscan_host(X, pts.w, self.eps, self.min_core_point)[0]
+        roots = np.unique(label[label >= 0])         # clusters in ascending label order
+        assign = np.where(label >= 0, np.searchsorted(roots, label), -1)
+        self.dims, self._dim_keys = dims, keys
+        self.core = pts
+        self.assign = assign.tolist()
+        self.n_clusters = int(roots.size)
+        self.n_noise = int((label < 0).sum())
+        self._performed = True
+        self.revision += 1
+
     def _recluster(self) -> None:
+        if self.method == "dbscan":
+            return self._recluster_dbscan()
         torch = self._t()
         pts = self._all_core()
         if len(pts) < self.k:
@@ -413,6 +508,7 @@ class Clustering:
             self.assign = em_assign.cpu().tolist()   # the EM kernel's final E-step argmax
         else:
             self.assign = self._assign(X).cpu().tolist()
+        self._performed = True
         self.revision += 1
 
     def _log_resp(self, X, C, var, pi):
@@ -447,8 +543,10 @@ class Clustering:
             return self._log_resp(X, self.centers, self.variances, self.mix_weights).argmax(1)
         return self._sqdist(X, self.centers).argmin(1)
 
-    def _check(self) -> None:
-        if self.centers is None:
+    def _check(self, query: str | None = None) -> None:
+        if query is not None and self.method == "dbscan":
+            raise NotSupported(query, self.method)
+        if not self._performed:
             raise NotPerformed()
 
     def _center_datum(self, j: int) -> Datum:
@@ -463,7 +561,7 @@ class Clustering:
 
     def get_k_center(self) -> list[Datum]:
         with self._lock:
-            self._check()
+            self._check("get_k_center")
             return [self._center_datum(j) for j in range(self.centers.shape[0])]
 
     def _nearest(self, d) -> int:
@@ -477,20 +575,22 @@ class Clustering:
 
     def get_nearest_center(self, d) -> Datum:
         with self._lock:
-            self._check()
+            self._check("get_nearest_center")
             return self._center_datum(self._nearest(d))
 
     def get_core_members(self) -> list[list[tuple[float, Datum]]]:
         with self._lock:
             self._check()
-            out: list[list[tuple[float, Datum]]] = [[] for _ in range(self.centers.shape[0])]
+            nc = self.n_clusters if self.method == "dbscan" else self.centers.shape[0]
+            out: list[list[tuple[float, Datum]]] = [[] for _ in range(nc)]
             for i, a in enumerate(self.assign):
-                out[a].append((float(self.core.w[i]), self.core.datum(i)))
+                if a >= 0:                           # dbscan: noise belongs to no cluster
+                    out[a].append((float(self.core.w[i]), self.core.datum(i)))
             return out
 
     def get_nearest_members(self, d) -> list[tuple[float, Datum]]:
         with self._lock:
-            self._check()
+            self._check("get_nearest_members")
             j = self._nearest(d)
             return [(float(self.core.w[i]), self.core.datum(i)) for i, a in enumerate(self.assign)
                     if a == j]
@@ -546,7 +646,11 @@ class Clustering:
             self.revision = rev
 
     def get_status(self) -> dict[str, str]:
-        return {"method": self.method, "k": str(self.k), "revision": str(self.revision),
-                "pending": str(len(self.pending)), "buckets": str(len(self.buckets)),
-                "compressor_method": self.compressor, "storage": "hbm" if self.gpu else "host",
-                "converter": "native" if self._native is not None else "python"}
+        st = {"method": self.method, "k": str(self.k), "revision": str(self.revision),
+              "pending": str(len(self.pending)), "buckets": str(len(self.buckets)),
+              "compressor_method": self.compressor, "storage": "hbm" if self.gpu else "host",
+              "converter": "native" if self._native is not None else "python"}
+        if self.method == "dbscan":
+            st.update(eps=repr(self.eps), min_core_point=repr(self.min_core_point),
+                      clusters=str(self.n_clusters), noise=str(self.n_noise))
+        return st

@@ -145,7 +145,47 @@ _SIGS = {
     "jb_sqdist_mfma": [_c_void_p, _i64, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
                        _c_void_p],
     "jb_argmin_rows": [_c_void_p, _i64, _i32, _c_void_p, _c_void_p],
+    "jb_dbscan": [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _f32, _f32, _c_void_p, _c_void_p,
+                  _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
 }
+
+DBSCAN_MAX_N = 65536        # csrc/hip/dbscan.hip kDbscanMaxN: the bitmap is n * n / 8 bytes
+
+
+def dbscan(X: torch.Tensor, w: torch.Tensor, eps: float, min_core_point: float):
+    """DBSCAN of the weighted points X [n, d] (csrc/hip/dbscan.hip, semantics in
+    docs/clustering_dbscan.md) -> (label int32 [n]: the smallest point index of
+    the point's cluster, -1 for noise; mass float32 [n]; adj int64 [n, nw]: the
+    adjacency bitmap, bit j & 63 of word j >> 6 of row i). One launch chain on
+    the current stream; the status word is read back at the end."""
+    if not isinstance(X, torch.Tensor) or X.dim() != 2 or not isinstance(w, torch.Tensor) or w.dim() != 1:
+        raise ValueError("dbscan: X must be [n, d] and w [n]")
+    n, d = X.shape
+    if n < 1 or d < 1 or w.numel() != n:
+        raise ValueError("dbscan: bad operand shapes")
+    if n > DBSCAN_MAX_N:
+        raise ValueError(f"dbscan: n = {n} over the limit of {DBSCAN_MAX_N} points")
+    eps, min_core_point = float(eps), float(min_core_point)
+    if not (0.0 < eps < math.inf) or not (0.0 < min_core_point < math.inf):
+        raise ValueError("dbscan: eps and min_core_point must be positive and finite")
+    _dev(X, torch.float32, "X")
+    _dev(w, torch.float32, "w")
+    dev = X.device
+    nw = (n + 63) // 64
+    xn2 = (X * X).sum(1).contiguous()
+    adj = torch.empty((n, nw), dtype=torch.int64, device=dev)
+    mass = torch.empty(n, dtype=torch.float32, device=dev)
+    core = torch.empty(nw, dtype=torch.int64, device=dev)
+    parent = torch.empty(n, dtype=torch.int32, device=dev)
+    label = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    rc = _fn("jb_dbscan")(_p(X), n, d, _p(xn2), _p(w), eps * eps, min_core_point, _p(adj), _p(mass),
+                          _p(core), _p(parent), _p(label), _p(status), _stream())
+    _check(rc, "jb_dbscan")
+    st = int(status.item())
+    if st != 0:
+        raise RuntimeError(f"jb_dbscan: a bounded loop ran out (status {st})")
+    return label, mass, adj
 
 
 def argmin_rows(D: torch.Tensor) -> torch.Tensor:

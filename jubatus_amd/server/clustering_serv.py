@@ -4,7 +4,10 @@ push(list<datum>) [update], get_revision, get_core_members, get_k_center,
 get_nearest_center(datum), get_nearest_members(datum) [analysis], clear
 (clustering.idl:26-44). ``weighted_datum`` travels as [weight, datum].
 Queries before the first clustering raise "clustering is not performed yet"
-(the reference's not_performed exception).
+(the reference's not_performed exception). With ``method: dbscan`` the three
+center queries raise the driver's NotSupported ("get_k_center is not supported
+by dbscan"); like NotPerformed it is a RuntimeError, so the RPC layer sends
+its text as the call's error and nothing here has to translate it.
 """
 from __future__ import annotations
 

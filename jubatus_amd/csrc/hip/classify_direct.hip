@@ -15,6 +15,7 @@
 // completion flag; the host spins on the flags (an empty launch + spin is
 // ~7 us on MI355X, a blocking stream sync adds ~5 us of interrupt wakeup).
 // Requests that do not fit take the batch path.
+#include "jb_hip_api.h"
 #include "jb_host_wait.hpp"
 #include "jb_linear.hpp"
 

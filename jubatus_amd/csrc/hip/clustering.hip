@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "jb_device.hpp"
+#include "jb_hip_api.h"
 
 namespace jb {
 

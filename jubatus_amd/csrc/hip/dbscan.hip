@@ -52,6 +52,7 @@
 #include <math.h>
 
 #include "jb_device.hpp"
+#include "jb_hip_api.h"
 
 namespace jb {
 

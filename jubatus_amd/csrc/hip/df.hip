@@ -23,6 +23,7 @@
 #include <hipcub/device/device_scan.hpp>
 
 #include "jb_device.hpp"
+#include "jb_hip_api.h"
 
 namespace jb {
 

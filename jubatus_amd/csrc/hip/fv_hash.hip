@@ -16,6 +16,7 @@
 // and no atomics/compaction are needed. Slots whose key does not match a
 // rule's key matcher are emitted as idx=-1 (skipped by every consumer).
 #include "jb_fv.hpp"
+#include "jb_hip_api.h"
 
 namespace jb {
 

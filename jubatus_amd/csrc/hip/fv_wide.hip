@@ -20,6 +20,7 @@
 //   fvw_comb_kernel    combination pairs (name matchers on the segments,
 //                      FNV-1a continued from the left name's state)
 #include "jb_fv.hpp"
+#include "jb_hip_api.h"
 
 namespace jb {
 

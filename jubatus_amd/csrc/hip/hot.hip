@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "jb_hip_api.h"
+
 namespace jb {
 
 constexpr int kHotTab = 4096;       // LDS slots per block (2x the slots of a chunk:

@@ -1,5 +1,5 @@
-// Argument block of jb_train_batch_submit (csrc/hip/train_batch.hip): one
-// GPU-scan train batch. Shared by the HIP library, the ctypes mirror
+// Argument block of jb_train_batch_submit (csrc/hip/train_batch.hip,
+// declared in jb_hip_api.h): one GPU-scan train batch. Shared by the HIP library, the ctypes mirror
 // (ops/hip.py TrainBatchArgs) and the native server (csrc/server).
 #ifndef JUBATUS_AMD_CSRC_HIP_JB_TRAIN_BATCH_HPP_
 #define JUBATUS_AMD_CSRC_HIP_JB_TRAIN_BATCH_HPP_
@@ -74,9 +74,5 @@ struct JbTrainBatch {
   // 1: W is a bf16 table (uint16 bit patterns; jb_linear_train_bf16)
   int64_t w_bf16;
 };
-
-extern "C" int64_t jb_train_batch_args_bytes();
-// 0 ok, 1 a launch helper refused its arguments, 2 a HIP runtime error
-extern "C" int jb_train_batch_submit(const JbTrainBatch* a);
 
 #endif  // JUBATUS_AMD_CSRC_HIP_JB_TRAIN_BATCH_HPP_

@@ -35,6 +35,7 @@
 //            precision form keeps every P positive
 // Loads use the agent-scope (sc1) path so a stream sees the latest L2
 // contents instead of a stale L1 line.
+#include "jb_hip_api.h"
 #include "jb_linear.hpp"
 
 namespace jb {
@@ -785,26 +786,6 @@ __global__ void mix_apply_kernel(float* __restrict__ w, const float* __restrict_
 
 }  // namespace jb
 
-// hot_rows / hot_n (device): rows to keep in the block LDS replica (nullptr:
-// none; only the concurrent modes with LC <= 64 use them); hot_rep: the
-// delta shards (jb_hot_rep_bytes(), zero-initialised once, left zero). stats (device,
-// 2 x u64, nullable): += samples that updated, samples with a valid label.
-// touched (device, H bytes, nullable): set to 1 for every row an update wrote.
-// mode kSerial (several streams, serial-equivalent result, serial.hip) needs
-// n_max >= the batch's sample count and scratch of jb_serial_scratch_bytes_lc(n_max, LC).
-extern "C" int64_t jb_serial_scratch_bytes(int64_t n_max);
-extern "C" int jb_serial_prepare(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
-                                 const int32_t* labels, const int64_t* stream_ptr, int nstreams,
-                                 int64_t n_max, float* W, float* S, const int32_t* active, int LC,
-                                 int method, float C, unsigned long long* stats, uint8_t* touched,
-                                 void* scratch, int64_t scratch_bytes, int bail_after,
-                                 hipStream_t stream);
-// stepper.hip: one stream of samples applied in order from an LDS row cache
-extern "C" int jb_stepper_train(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
-                                const int32_t* labels, const int64_t* range, float* W, float* P,
-                                const int32_t* active, int LC, int method, float C, unsigned long long* stats,
-                                uint8_t* touched, int* err, hipStream_t stream);
-extern "C" int jb_stepper_enabled();
 // exact steps per 1024-sample committer round past which the rest of a
 // kSerial batch goes to the sequential kernel (an exact step costs a few
 // times a sequential sample; see serial.hip)

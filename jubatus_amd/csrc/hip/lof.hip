@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "jb_device.hpp"
+#include "jb_hip_api.h"
 #include "jb_host_wait.hpp"
 
 namespace jb {

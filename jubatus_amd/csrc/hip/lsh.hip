@@ -17,6 +17,7 @@
 // and over CSR rows (exact cosine / euclid for inverted_index), writing a
 // score per row; top-k selection then runs on the score vector.
 #include "jb_device.hpp"
+#include "jb_hip_api.h"
 #include "jb_host_wait.hpp"
 
 #include <cstring>
@@ -256,13 +257,6 @@ extern "C" int jb_sparse_scan(const int32_t* qidx, const float* qval, int qn, fl
                      qnorm2, row_ptr, ridx, rval, rnorm2, valid, nrows, metric, out);
   return (int)hipGetLastError();
 }
-
-extern "C" int jb_topk_direct_query(const uint64_t* qbits, const float* qnorm, int nq,
-                                    const uint64_t* tbits, const float* tnorm,
-                                    const uint8_t* valid, int64_t nrows, int words, int hash_num,
-                                    int metric, int k, float* scratch_d, int32_t* scratch_i,
-                                    float* out_d_host, int32_t* out_i_host, uint32_t* done_host,
-                                    hipStream_t stream);
 
 // Latency path of similar_row / neighbor_row (lsh family): the host-hashed
 // query CSR (row_ptr[nq+1] host, idx / val host) rides in the kernel

@@ -16,6 +16,7 @@
 #include <hipcub/iterator/counting_input_iterator.hpp>
 
 #include "jb_device.hpp"
+#include "jb_hip_api.h"
 
 namespace jb {
 

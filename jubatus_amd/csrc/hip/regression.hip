@@ -46,6 +46,7 @@
 //
 // Known limit: the statistics are fp32 sums, and sum2/count - mean^2 cancels;
 // the stddev is lost once |mean| / stddev reaches a few thousand.
+#include "jb_hip_api.h"
 #include "jb_linear.hpp"
 
 namespace jb {
@@ -341,10 +342,10 @@ __global__ __launch_bounds__(256) void regression_train_m_kernel(
 
 }  // namespace jb
 
-extern "C" int jb_regression_train(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
-                                   const float* targets, const int64_t* stream_ptr, int nstreams,
-                                   float* W, float* stats, float C, float eps, int concurrent,
-                                   hipStream_t stream) {
+// PA keeps its own kernel (docs/PERFORMANCE.md); jb_regression_train_m forwards here
+static int launch_pa(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
+                     const float* targets, const int64_t* stream_ptr, int nstreams, float* W,
+                     float* stats, float C, float eps, int concurrent, hipStream_t stream) {
   if (nstreams <= 0) return 0;
   const int threads = 256, blocks = (nstreams * 64 + threads - 1) / threads;
   if (concurrent)
@@ -356,20 +357,15 @@ extern "C" int jb_regression_train(const int64_t* row_ptr, const int32_t* fidx, 
   return (int)hipGetLastError();
 }
 
-// method: models/linear_oracle.py METHOD_IDS (Method of jb_linear.hpp). PA
-// launches regression_train_kernel, exactly as jb_regression_train does. C is
-// the regularization weight (perceptron: the learning rate). P: the precision
-// table of CW / AROW / NHERD, null otherwise. slot_scratch: as many floats as
-// fval, for those three methods; may be null when no sample has more than 256
-// slots.
+// the one train entry point: contract in jb_hip_api.h
 extern "C" int jb_regression_train_m(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
                                      const float* targets, const int64_t* stream_ptr, int nstreams,
                                      float* W, float* P, float* stats, float* slot_scratch,
                                      int method, float C, float eps, int concurrent,
                                      hipStream_t stream) {
   if (method == jb::PA)
-    return jb_regression_train(row_ptr, fidx, fval, targets, stream_ptr, nstreams, W, stats, C, eps,
-                               concurrent, stream);
+    return launch_pa(row_ptr, fidx, fval, targets, stream_ptr, nstreams, W, stats, C, eps,
+                     concurrent, stream);
   if (method < jb::PERCEPTRON || method > jb::NHERD) return (int)hipErrorInvalidValue;
   if (method >= jb::CW && P == nullptr) return (int)hipErrorInvalidValue;
   if (nstreams <= 0) return 0;

@@ -42,6 +42,7 @@
 #include <stdint.h>
 
 #include "jb_device.hpp"
+#include "jb_hip_api.h"
 
 namespace jb {
 namespace {

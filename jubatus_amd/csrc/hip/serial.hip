@@ -36,6 +36,7 @@
 // These kernels (the bound committer) serve label capacities past 64. The
 // entry point jb_serial_prepare hands capacities up to 64 to the verified
 // committer (vcommit.hip) and sizes its segment budget.
+#include "jb_hip_api.h"
 #include "jb_linear.hpp"
 #include "jb_serial_layout.hpp"
 #include <cstdio>
@@ -822,13 +823,6 @@ static int64_t* segments_seen(void* scratch) {
   seen[scratch] = p;
   return p;
 }
-
-// vcommit.hip: the verified committer (label capacities <= 64)
-extern "C" int jb_vcommit_prepare(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
-                                  const int32_t* labels, const int64_t* stream_ptr, int nstreams, int64_t n_max,
-                                  float* W, float* S, const int32_t* active, int LC, int method, float C,
-                                  unsigned long long* stats, uint8_t* touched, void* scratch, int nseg,
-                                  hipStream_t stream);
 
 // a scratch buffer's owner (re)allocated it: the pinned words of a freed
 // buffer that had the same address must not carry its segment history over

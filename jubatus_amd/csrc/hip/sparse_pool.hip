@@ -33,6 +33,7 @@
 #include <algorithm>
 
 #include "jb_device.hpp"
+#include "jb_hip_api.h"
 
 namespace jb {
 
@@ -335,11 +336,6 @@ extern "C" int jb_pool_scan(const int64_t* qptr, const int32_t* qidx, const floa
 #undef JB_LAUNCH_DEV
   return (int)hipGetLastError();
 }
-
-extern "C" int jb_topk_scores_direct(const float* src_d, int flip, int nq, int64_t nrows, int k,
-                                     float* scratch_d, int32_t* scratch_i, float* out_d_host,
-                                     int32_t* out_i_host, uint32_t* done_host,
-                                     hipStream_t stream);   // topk.hip
 
 // Latency path: nq (<= 8) queries given on the host - a CSR of hashed
 // features (any order, repeats, idx < 0 dropped: normalized here) or stored

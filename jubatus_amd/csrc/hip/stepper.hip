@@ -46,6 +46,7 @@
 // time limit (an error code instead of a hung GPU).
 #include <string.h>
 
+#include "jb_hip_api.h"
 #include "jb_linear.hpp"
 #include "jb_vc_state.hpp"
 

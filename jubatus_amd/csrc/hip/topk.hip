@@ -28,6 +28,7 @@
 #include <stdlib.h>
 
 #include "jb_device.hpp"
+#include "jb_hip_api.h"
 #include "jb_host_wait.hpp"
 
 namespace jb {

@@ -16,39 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-extern "C" int jb_scan_train(const uint8_t* buf, const int64_t* req_off, const int64_t* req_len,
-                             const int64_t* sample_base, int R, const uint64_t* lt_hash,
-                             const int32_t* lt_meta, int lt_cap, const uint8_t* lt_blob,
-                             int lt_blob_len, int sps, int spn, int64_t* datum_off,
-                             int32_t* datum_len, int32_t* labels, int64_t* row_ptr,
-                             int64_t* req_slots, uint32_t* hist, int nhist, int32_t* err,
-                             uint8_t* empty_at, int64_t empty_off, int32_t* host_out,
-                             hipStream_t stream);
-extern "C" int jb_fv_hash(const uint8_t* buf, int64_t buf_len, int64_t buf_cap,
-                          const int64_t* datum_off, const int32_t* datum_len,
-                          const int64_t* row_ptr, int n, const void* srules, int n_srules,
-                          const void* nrules, int n_nrules, const uint8_t* blob, int blob_len,
-                          uint64_t H, int32_t* out_idx, float* out_val, int32_t* err,
-                          hipStream_t stream);
-extern "C" int jb_hot_detect(const int64_t* row_ptr, int n, const int32_t* fidx, int64_t max_slots,
-                             int block_min, int min_count, int max_rows, int32_t* gkey,
-                             int32_t* gcnt, int gcap, int32_t* hot_rows, int32_t* hot_n,
-                             hipStream_t stream);
-extern "C" int jb_linear_train(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
-                               const int32_t* labels, const int64_t* stream_ptr, int nstreams,
-                               float* W, float* S, const int32_t* active, int LC, int method,
-                               float C, int mode, const int32_t* hot_rows, const int32_t* hot_n,
-                               float* hot_rep, int merge_every, int hot_waves,
-                               unsigned long long* stats, uint8_t* touched, int64_t n_max,
-                               void* scratch, int64_t scratch_bytes, hipStream_t stream);
-extern "C" int jb_linear_train_bf16(const int64_t* row_ptr, const int32_t* fidx,
-                                    const float* fval, const int32_t* labels,
-                                    const int64_t* stream_ptr, int nstreams, uint16_t* W,
-                                    float* S, const int32_t* active, int LC, int method, float C,
-                                    int mode, unsigned long long* stats, uint8_t* touched,
-                                    void* scratch, int64_t scratch_bytes, hipStream_t stream);
-
-#include "jb_train_batch.hpp"
+#include "jb_hip_api.h"
 
 #define JB_TRY(x) do { if ((x) != hipSuccess) return 2; } while (0)
 

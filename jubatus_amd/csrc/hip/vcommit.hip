@@ -61,6 +61,7 @@
 #include <type_traits>
 
 #include "jb_commit.hpp"
+#include "jb_hip_api.h"
 #include "jb_vc_state.hpp"
 
 namespace jb {
@@ -1109,17 +1110,6 @@ __global__ __launch_bounds__(256) void vc_verify_kernel(
 
 // bytes of the verified committer's fixed region (jb_serial_layout.hpp)
 extern "C" int64_t jb_vcommit_fixed_bytes() { return jb::kVcFixed; }
-
-// stepper.hip
-extern "C" int jb_stepper_enabled();
-extern "C" int jb_stepper_chunk(const int64_t* row_ptr, const int32_t* fidx, const float* fval, const int32_t* labels,
-                                float* W, float* P, const int32_t* active, int LC, int method, float C,
-                                unsigned long long* stats, uint8_t* touched, int64_t* vst, int64_t* vtail,
-                                hipStream_t stream);
-extern "C" int jb_stepper_cand(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
-                               const int32_t* labels, float* W, float* P, const int32_t* active, int LC, int method,
-                               float C, int64_t* vst, const int4* aux, int32_t* g_key, float* g_rmax, float* g_dw,
-                               float* g_dp, hipStream_t stream);
 
 template <int L>
 static int launch_vc(int method, const int64_t* row_ptr, const int32_t* fidx, const float* fval,

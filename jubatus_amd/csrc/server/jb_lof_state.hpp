@@ -16,43 +16,8 @@
 #include <deque>
 #include <vector>
 
+#include "jb_hip_api.h"
 #include "jb_server_common.hpp"
-
-extern "C" {
-int jb_lof_mark(int64_t nrows, int k, const int32_t* nb_slot, const int32_t* changed,
-                const int32_t* nchanged, int clear_ok, uint8_t* ok, uint8_t* lrd_ok,
-                hipStream_t stream);
-int jb_lof_set_lists(int n, const int32_t* slots, const int32_t* cs, const float* cd, int kk, int k,
-                     int ignore_same, int32_t* nb_slot, float* nb_dist, float* kdist, uint8_t* ok,
-                     uint8_t* lrd_ok, int32_t* changed, int32_t* nchanged, hipStream_t stream);
-int jb_lof_add(int p, const int32_t* cs, const float* cd, int nc, int k, int ignore_same,
-               int64_t nrows, int32_t* nb_slot, float* nb_dist, float* kdist, uint8_t* ok,
-               float* lrd, uint8_t* lrd_ok, int32_t* changed, int32_t* nchanged,
-               uint32_t* out_host, int max_missing, hipStream_t stream);
-int jb_lof_add_st(int p, const int32_t* cs, const float* cd, int nc, int k, int ignore_same, int64_t nrows,
-                  int32_t* nb_slot, float* nb_dist, float* kdist, uint8_t* ok, float* lrd, uint8_t* lrd_ok,
-                  int32_t* changed, int32_t* nchanged, uint32_t* kstamp, uint32_t* lstamp, uint32_t epoch,
-                  uint32_t* out_host, int max_missing, hipStream_t stream);
-int jb_lof_add_many(int nadd, const int32_t* ps, const int32_t* cs, const float* cd, const int32_t* nc,
-                    int stride, int k, int ignore_same, int32_t* nb_slot, float* nb_dist, float* kdist,
-                    uint8_t* ok, float* lrd, uint8_t* lrd_ok, int32_t* changed, int32_t* nchanged,
-                    uint32_t* kstamp, uint32_t* lstamp, uint32_t epoch0, int32_t* cand, uint32_t* res,
-                    uint32_t* out_host, int out_stride, int max_missing, unsigned long long* prof,
-                    hipStream_t stream, int wait, uint32_t* chain);
-int jb_lof_add_many_wait(int nadd, uint32_t* out_host, int out_stride, hipStream_t stream);
-int jb_lof_score_st(const int32_t* ts, const float* td, int nt, int k, const int32_t* nb_slot,
-                    const float* nb_dist, const float* kdist, const uint8_t* ok, float* lrd, uint8_t* lrd_ok,
-                    int store_slot, const uint32_t* kstamp, uint32_t* lstamp, uint32_t epoch,
-                    uint32_t* out_host, int max_missing, hipStream_t stream);
-int jb_lof_score_many(int nq, const int32_t* ts, const float* td, const int32_t* nt, int stride, int k,
-                      const int32_t* nb_slot, const float* nb_dist, const float* kdist, const uint8_t* ok, float* lrd,
-                      uint8_t* lrd_ok, const uint32_t* kstamp, uint32_t* lstamp, uint32_t epoch, uint32_t* out_host,
-                      int out_stride, int max_missing, hipStream_t stream);
-int jb_lof_invalidate(const int32_t* slots, int n, int64_t nrows, uint8_t* ok, uint8_t* lrd_ok,
-                      hipStream_t stream);
-void* jb_host_alloc(int64_t nbytes);
-int jb_host_free(void* p);
-}
 
 namespace jb {
 namespace row {

@@ -17,12 +17,9 @@
 #include <string>
 #include <vector>
 
+#include "jb_hip_api.h"
 #include "jb_mix_group.hpp"
 #include "jb_roctx.hpp"
-
-// csrc/hip/mix.hip
-extern "C" int jb_mix_pair_sum(float* p, const float* q, int64_t n, hipStream_t st);
-extern "C" int jb_mix_pair_max(uint8_t* p, const uint8_t* q, int64_t n, hipStream_t st);
 
 namespace jb {
 namespace mix {

@@ -35,58 +35,13 @@
 #include <utility>
 #include <vector>
 
+#include "jb_hip_api.h"
 #include "jb_hostfv.hpp"
 #include "jb_hostfv_wide.hpp"
 #include "jb_row_mix.hpp"
 #include "jb_server_common.hpp"
 #include "jb_wide_rules.hpp"
 #include "jb_value.hpp"
-
-extern "C" {
-int jb_signature(const int64_t* row_ptr, const int32_t* fidx, const float* fval, int n,
-                 int hash_num, uint64_t seed, int mode, uint64_t* bits, float* norms,
-                 hipStream_t stream);
-int jb_hamming_scan(const uint64_t* qbits, const float* qnorm, int nq, const uint64_t* tbits,
-                    const float* tnorm, const uint8_t* valid, int64_t nrows, int words,
-                    int hash_num, int metric, float* out, hipStream_t stream);
-int jb_lsh_query_direct(const int32_t* idx, const float* val, const int64_t* row_ptr, int nq,
-                        int hash_num, uint64_t seed, int mode, int metric, const uint64_t* tbits,
-                        const float* tnorm, const uint8_t* valid, int64_t nrows, int k,
-                        uint64_t* qbits_scratch, float* qnorm_scratch, float* scratch_d,
-                        int32_t* scratch_i, float* out_d_host, int32_t* out_i_host,
-                        uint32_t* done_host, hipStream_t stream);
-int jb_lsh_set_rows_direct(const int32_t* idx, const float* val, const int64_t* row_ptr, int n,
-                           const int64_t* slots, int hash_num, uint64_t seed, int mode,
-                           uint64_t* tbits, float* tnorm, uint8_t* valid, hipStream_t stream);
-int jb_lsh_set_rows_staged(const int64_t* rp, const int64_t* slots, const int32_t* idx, const float* val, int n,
-                           int hash_num, uint64_t seed, int mode, uint64_t* tbits, float* tnorm, uint8_t* valid,
-                           hipStream_t stream);
-int jb_topk_direct_query(const uint64_t* qbits, const float* qnorm, int nq, const uint64_t* tbits,
-                         const float* tnorm, const uint8_t* valid, int64_t nrows, int words,
-                         int hash_num, int metric, int k, float* scratch_d, int32_t* scratch_i,
-                         float* out_d_host, int32_t* out_i_host, uint32_t* done_host,
-                         hipStream_t stream);
-int jb_topk_blocks(int64_t nrows, int k);
-int64_t jb_topk_direct_scratch(int nq);
-int jb_topk_scratch_init(int32_t* scratch_i, hipStream_t stream);
-int jb_pool_scan(const int64_t* qptr, const int32_t* qidx, const float* qval, const double* qn2,
-                 const int32_t* qslots, int nq, int qtot, const int64_t* r_off,
-                 const int32_t* r_len, const double* r_n2, const uint8_t* valid, int64_t nrows,
-                 const int32_t* p_idx, const float* p_val, int metric, int lpr, float* out,
-                 hipStream_t stream);
-int jb_pool_query_direct(const int32_t* idx, const float* val, const int64_t* row_ptr,
-                         const int32_t* qslots, const int64_t* slot_len, int nq,
-                         const int64_t* r_off, const int32_t* r_len, const double* r_n2,
-                         const uint8_t* valid, int64_t nrows, const int32_t* p_idx,
-                         const float* p_val, int metric, int lpr, int k, float* scores,
-                         float* scratch_d, int32_t* scratch_i, float* out_d_host,
-                         int32_t* out_i_host, uint32_t* done_host, hipStream_t stream);
-int jb_pool_append(const uint8_t* pack, int n, int64_t nnz, int64_t base, int64_t* r_off,
-                   int32_t* r_len, double* r_n2, uint8_t* valid, int32_t* p_idx, float* p_val,
-                   hipStream_t stream);
-void* jb_host_alloc(int64_t nbytes);
-int jb_host_free(void* p);
-}
 
 namespace jb {
 namespace row {

@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "jb_hash.hpp"
+#include "jb_hip_api.h"
 #include "jb_roctx.hpp"
 #include "jb_host_linear.hpp"
 #include "jb_hostfv.hpp"
@@ -60,37 +61,6 @@
 #include "jb_train_batch.hpp"
 #include "jb_server_common.hpp"
 #include "jb_value.hpp"
-
-extern "C" int jb_linear_train(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
-                               const int32_t* labels, const int64_t* stream_ptr, int nstreams,
-                               float* W, float* S, const int32_t* active, int LC, int method,
-                               float C, int mode, const int32_t* hot_rows, const int32_t* hot_n,
-                               float* hot_rep, int merge_every, int hot_waves,
-                               unsigned long long* stats, uint8_t* touched, int64_t n_max,
-                               void* scratch, int64_t scratch_bytes, hipStream_t stream);
-extern "C" int64_t jb_serial_scratch_bytes_lc(int64_t n_max, int LC);
-extern "C" int jb_serial_scratch_forget(void* scratch);
-extern "C" int jb_linear_classify(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
-                                  int n_samples, const float* W, int LC, float* out,
-                                  hipStream_t stream);
-extern "C" int jb_classify_direct(const int32_t* idx, const float* val, const int64_t* row_ptr,
-                                  int n, const float* W, int LC, float* out_host,
-                                  uint32_t* done_host, hipStream_t stream);
-extern "C" int jb_mix_take(uint8_t* touched, uint8_t* mark, int64_t H, hipStream_t st);
-extern "C" int jb_mix_pack_bf16(const float* snap, int64_t n, int Lc, int has_s, uint16_t* wb, float* sb,
-                                hipStream_t st);
-extern "C" int jb_mix_unpack_bf16(const uint16_t* wb, const float* sb, int64_t n, int Lc, int has_s, float* red,
-                                  hipStream_t st);
-extern "C" int64_t jb_mix_compact_temp_bytes(int64_t H);
-extern "C" int jb_mix_compact(const uint8_t* mark, int64_t H, int64_t* rows, int64_t* count, void* temp,
-                              int64_t temp_bytes, hipStream_t st);
-extern "C" int jb_mix_gather(const float* W, const float* S, int LC, const int64_t* rows, int64_t n,
-                             const int32_t* map, int Lc, float* snap, hipStream_t st);
-extern "C" int jb_mix_fold(float* W, float* S, int LC, const int64_t* rows, int64_t n, const int32_t* map,
-                           int Lc, const float* snap, const float* red, float inv_n, hipStream_t st);
-extern "C" void* jb_host_alloc(int64_t nbytes);
-extern "C" int jb_host_free(void* p);
-extern "C" int64_t jb_hot_rep_bytes();
 
 namespace {
 

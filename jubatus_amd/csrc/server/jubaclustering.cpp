@@ -30,22 +30,13 @@
 #include <unordered_map>
 #include <vector>
 
+#include "jb_hip_api.h"
 #include "jb_host_server.hpp"
 #include "jb_linear_conv.hpp"
 #include "jb_mix_device.hpp"
 #include "jb_msgpack.hpp"
 #include "jb_pyrandom.hpp"
 #include "jb_wide_rules.hpp"
-
-extern "C" int jb_argmin_rows(const float* D, int64_t n, int k, int32_t* out, hipStream_t stream);
-extern "C" int jb_sqdist_mfma(const float* X, int64_t n, const float* C, int k, int d, const float* xn2,
-                              const float* cn2, float* out, hipStream_t stream);
-extern "C" int jb_kmeanspp(const float* X, int n, int d, const float* w, const double* u, int m, float* d2,
-                           float* prob, int32_t* out, int32_t* status, hipStream_t stream);
-extern "C" int jb_lloyd(const float* X, int n, int d, const float* w, float* C, int k, int iters, float atol,
-                        float rtol, int32_t* assign, float* S, int32_t* done_iters, hipStream_t stream);
-extern "C" int jb_gmm_em(const float* X, int n, int d, const float* w, float* C, float* var, float* pi, int k,
-                         int iters, int32_t* assign, hipStream_t stream);
 
 namespace {
 

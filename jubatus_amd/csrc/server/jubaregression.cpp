@@ -18,7 +18,7 @@
 //
 // Data path: the batch of queued train RPCs is validated and hashed on the
 // host (jb_hostfv.hpp, bit-identical to fv_hash.hip), one request per
-// update stream, and trained by ONE jb_regression_train launch (concurrent
+// update stream, and trained by ONE jb_regression_train_m launch (concurrent
 // streams when the batch holds several requests, like the Python server's
 // train_requests); estimate batches are hashed the same way and scored by
 // jb_regression_estimate. Model files are byte-compatible with the Python
@@ -36,6 +36,7 @@
 #include <string>
 #include <vector>
 
+#include "jb_hip_api.h"
 #include "jb_hostfv.hpp"
 #include "jb_linear_conv.hpp"
 #include "jb_mix_device.hpp"
@@ -43,24 +44,6 @@
 #include "jb_rpc.hpp"
 #include "jb_server_common.hpp"
 #include "jb_value.hpp"
-
-extern "C" int jb_mix_gather(const float* W, const float* S, int LC, const int64_t* rows, int64_t n,
-                             const int32_t* map, int Lc, float* snap, hipStream_t st);
-extern "C" int jb_mix_fold(float* W, float* S, int LC, const int64_t* rows, int64_t n, const int32_t* map,
-                           int Lc, const float* snap, const float* red, float inv_n, hipStream_t st);
-
-extern "C" int jb_regression_train(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
-                                   const float* targets, const int64_t* stream_ptr, int nstreams,
-                                   float* W, float* stats, float C, float eps, int concurrent,
-                                   hipStream_t stream);
-extern "C" int jb_regression_train_m(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
-                                     const float* targets, const int64_t* stream_ptr, int nstreams,
-                                     float* W, float* P, float* stats, float* slot_scratch,
-                                     int method, float C, float eps, int concurrent,
-                                     hipStream_t stream);
-extern "C" int jb_regression_estimate(const int64_t* row_ptr, const int32_t* fidx,
-                                      const float* fval, int n, const float* W, float* out,
-                                      hipStream_t stream);
 
 namespace {
 
@@ -206,18 +189,12 @@ class Regression : public jb::mix::Mixable {
     upload(n, slots);
     HIPCHK(hipMemcpyAsync(d_tgt_.get(n), tgt_.p, 4 * (size_t)n, hipMemcpyHostToDevice, stream_));
     HIPCHK(hipMemcpyAsync(d_sp_.get(sp.size()), sp.data(), 8 * sp.size(), hipMemcpyHostToDevice, stream_));
-    int rc;
-    if (cfg_.method == "PA") {
-      rc = jb_regression_train(d_row_.p, d_idx_.p, d_val_.p, d_tgt_.p, d_sp_.p, ns, w_, stats_, cfg_.C,
-                               cfg_.eps, ns > 1 ? 1 : 0, stream_);
-    } else {
-      // d_scratch_: one float per slot, where the kernel parks the P
-      // increments of samples wider than its register slots
-      float* scratch = cfg_.cov ? d_scratch_.get(std::max<int64_t>(slots, 1)) : nullptr;
-      rc = jb_regression_train_m(d_row_.p, d_idx_.p, d_val_.p, d_tgt_.p, d_sp_.p, ns, w_, p_, stats_, scratch,
-                                 cfg_.mid, cfg_.C, cfg_.eps, ns > 1 ? 1 : 0, stream_);
-    }
-    if (rc != 0) throw std::runtime_error("jb_regression_train failed: " + std::to_string(rc));
+    // d_scratch_: one float per slot, where the kernel parks the P
+    // increments of samples wider than its register slots
+    float* scratch = cfg_.cov ? d_scratch_.get(std::max<int64_t>(slots, 1)) : nullptr;
+    const int rc = jb_regression_train_m(d_row_.p, d_idx_.p, d_val_.p, d_tgt_.p, d_sp_.p, ns, w_, p_, stats_,
+                                         scratch, cfg_.mid, cfg_.C, cfg_.eps, ns > 1 ? 1 : 0, stream_);
+    if (rc != 0) throw std::runtime_error("jb_regression_train_m failed: " + std::to_string(rc));
     HIPCHK(hipStreamSynchronize(stream_));
     samples_ += (uint64_t)n;
   }

@@ -19,134 +19,147 @@ from ..utils import trace
 
 _c_void_p = ctypes.c_void_p
 _i32 = ctypes.c_int32
+_u32 = ctypes.c_uint32
 _i64 = ctypes.c_int64
 _u64 = ctypes.c_uint64
 _f32 = ctypes.c_float
 
+# name -> (return type, argument types), as csrc/hip/jb_hip_api.h declares
+# them (tests/test_hip_abi.py compares the two type by type): a pointer or a
+# stream is _c_void_p, None a void return
 _SIGS = {
-    "jb_train_batch_submit": [_c_void_p],
-    "jb_train_batch_args_bytes": [],
-    "jb_event_create": [],
-    "jb_event_destroy": [_i64],
-    "jb_event_record": [_i64, _c_void_p],
-    "jb_stream_wait_event": [_c_void_p, _i64],
-    "jb_event_query": [_i64],
-    "jb_event_sync": [_i64],
-    "jb_fv_hash": [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32,
-                   _c_void_p, _i32, _c_void_p, _i32, _u64, _c_void_p, _c_void_p, _c_void_p,
-                   _c_void_p],
-    "jb_linear_train": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p,
-                        _c_void_p, _c_void_p, _i32, _i32, _f32, _i32, _c_void_p, _c_void_p,
-                        _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i64, _c_void_p, _i64,
-                        _c_void_p],
-    "jb_linear_train_bf16": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
-                             _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _f32, _i32, _c_void_p,
-                             _c_void_p, _c_void_p, _i64, _c_void_p],
-    "jb_linear_classify_bf16": [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32,
-                                _c_void_p, _c_void_p],
-    "jb_classify_direct_bf16": [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32,
-                                _c_void_p, _c_void_p, _c_void_p],
-    "jb_hot_rep_bytes": [],
-    "jb_df_scratch_bytes": [_i64, _i64],
-    "jb_df_weigh": [_c_void_p, _i32, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64,
-                    _i64, _i32, _c_void_p, _i64, _c_void_p, _c_void_p],
-    "jb_serial_scratch_bytes": [_i64],
-    "jb_serial_scratch_bytes_lc": [_i64, _i32],
-    "jb_serial_scratch_forget": [_c_void_p],
-    "jb_stepper_error": [],
-    "jb_stepper_prof": [_c_void_p],
-    "jb_hot_detect": [_c_void_p, _i32, _c_void_p, _i64, _i32, _i32, _i32, _c_void_p, _c_void_p,
-                      _i32, _c_void_p, _c_void_p, _c_void_p],
-    "jb_linear_classify": [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32, _c_void_p,
-                           _c_void_p],
-    "jb_scale": [_c_void_p, _i64, _f32, _c_void_p],
-    "jb_regression_train": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
-                            _c_void_p, _c_void_p, _f32, _f32, _i32, _c_void_p],
-    "jb_regression_train_m": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
-                              _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _f32, _f32, _i32,
-                              _c_void_p],
-    "jb_regression_estimate": [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
-                               _c_void_p],
-    "jb_signature": [_c_void_p, _c_void_p, _c_void_p, _i32, _i32, _u64, _i32, _c_void_p,
-                     _c_void_p, _c_void_p],
-    "jb_hamming_scan": [_c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64, _i32,
-                        _i32, _i32, _c_void_p, _c_void_p],
-    "jb_sparse_scan": [_c_void_p, _c_void_p, _i32, _f32, _c_void_p, _c_void_p, _c_void_p,
-                       _c_void_p, _c_void_p, _i64, _i32, _c_void_p, _c_void_p],
-    "jb_mix_apply": [_c_void_p, _c_void_p, _c_void_p, _i64, _f32, _c_void_p],
-    "jb_classify_direct": [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32, _c_void_p,
-                           _c_void_p, _c_void_p],
-    "jb_topk": [_i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _i32,
-                _i32, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
-    "jb_nn_reduce": [_c_void_p, _c_void_p, _i32, _i32, _c_void_p, _i32, _i32, _f32, _c_void_p,
-                     _c_void_p, _c_void_p],
-    "jb_topk_blocks": [_i64, _i32],
-    "jb_topk_mq_stats": [_c_void_p],
-    "jb_topk_direct_scratch": [_i32],
-    "jb_topk_scratch_init": [_c_void_p, _c_void_p],
-    "jb_topk_set_prof": [_c_void_p],
-    "jb_topk_direct_query_path": [_c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64,
-                                  _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
-                                  _c_void_p, _c_void_p, _i32, _c_void_p],
-    "jb_topk_scores_direct_path": [_c_void_p, _i32, _i32, _i64, _i32, _c_void_p, _c_void_p,
-                                   _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p],
-    "jb_lsh_query_direct": [_c_void_p, _c_void_p, _c_void_p, _i32, _i32, _u64, _i32, _i32, _c_void_p,
-                            _c_void_p, _c_void_p, _i64, _i32, _c_void_p, _c_void_p, _c_void_p,
-                            _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
-    "jb_lsh_set_rows_direct": [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32, _u64, _i32,
-                               _c_void_p, _c_void_p, _c_void_p, _c_void_p],
-    "jb_pool_query_direct": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
-                             _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p,
-                             _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
-                             _c_void_p, _c_void_p, _c_void_p, _c_void_p],
-    "jb_topk_scores_direct": [_c_void_p, _i32, _i32, _i64, _i32, _c_void_p, _c_void_p, _c_void_p,
-                              _c_void_p, _c_void_p, _c_void_p],
-    "jb_topk_direct_query": [_c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64, _i32,
-                            _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                            _c_void_p, _c_void_p],
-    "jb_diag_empty": [_c_void_p, _i32, _c_void_p],
-    "jb_scan_train": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _i32,
-                      _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                      _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _i64, _c_void_p,
-                      _c_void_p],
-    "jb_scan_train_profile": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
-                              _i32, _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
-                              _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
-                              _c_void_p],
-    "jb_pool_scan": [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _c_void_p,
-                     _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _i32, _i32,
-                     _c_void_p, _c_void_p],
-    "jb_pool_append": [_c_void_p, _i32, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                       _c_void_p, _c_void_p, _c_void_p],
-    "jb_lof_add": [_i32, _c_void_p, _c_void_p, _i32, _i32, _i32, _i64, _c_void_p, _c_void_p,
-                   _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                   _i32, _c_void_p],
-    "jb_lof_mark": [_i64, _i32, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
-                    _c_void_p],
-    "jb_lof_set_lists": [_i32, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _c_void_p,
-                         _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                         _c_void_p],
-    "jb_lof_score": [_c_void_p, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                     _c_void_p, _c_void_p, _i32, _c_void_p, _i32, _c_void_p],
-    "jb_fvw_count": [_c_void_p, _i64, _c_void_p, _c_void_p, _i32, _c_void_p, _i32, _c_void_p, _i32,
-                     _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
-    "jb_fvw_emit": [_c_void_p, _i64, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _i32,
-                    _c_void_p, _i32, _c_void_p, _u64, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
-                    _c_void_p, _c_void_p, _c_void_p],
-    "jb_fvw_comb": [_c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
-                    _c_void_p, _u64, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
-    "jb_fvw_name_bytes": [],
-    "jb_kmeanspp": [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
-                    _c_void_p, _c_void_p, _c_void_p],
-    "jb_gmm_em": [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _c_void_p,
-                  _c_void_p],
-    "jb_lloyd": [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _f32, _f32, _c_void_p,
-                 _c_void_p, _c_void_p, _c_void_p],
-    "jb_sqdist_mfma": [_c_void_p, _i64, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
-                       _c_void_p],
-    "jb_argmin_rows": [_c_void_p, _i64, _i32, _c_void_p, _c_void_p],
-    "jb_dbscan": [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _f32, _f32, _c_void_p, _c_void_p,
-                  _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p],
+    "jb_train_batch_submit": (_i32, [_c_void_p]),
+    "jb_train_batch_args_bytes": (_i64, []),
+    "jb_event_create": (_i64, []),
+    "jb_event_destroy": (_i32, [_i64]),
+    "jb_event_record": (_i32, [_i64, _c_void_p]),
+    "jb_stream_wait_event": (_i32, [_c_void_p, _i64]),
+    "jb_event_query": (_i32, [_i64]),
+    "jb_event_sync": (_i32, [_i64]),
+    "jb_fv_hash": (_i32, [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p,
+                          _i32, _c_void_p, _i32, _c_void_p, _i32, _u64, _c_void_p, _c_void_p,
+                          _c_void_p, _c_void_p]),
+    "jb_linear_train": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
+                               _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _f32, _i32, _c_void_p,
+                               _c_void_p, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i64,
+                               _c_void_p, _i64, _c_void_p]),
+    "jb_linear_train_bf16": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
+                                    _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _f32, _i32,
+                                    _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p]),
+    "jb_linear_classify_bf16": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32,
+                                       _c_void_p, _c_void_p]),
+    "jb_classify_direct_bf16": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32,
+                                       _c_void_p, _c_void_p, _c_void_p]),
+    "jb_hot_rep_bytes": (_i64, []),
+    "jb_df_scratch_bytes": (_i64, [_i64, _i64]),
+    "jb_df_weigh": (_i32, [_c_void_p, _i32, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                           _c_void_p, _i64, _i64, _i32, _c_void_p, _i64, _c_void_p, _c_void_p]),
+    "jb_serial_scratch_bytes": (_i64, [_i64]),
+    "jb_serial_scratch_bytes_lc": (_i64, [_i64, _i32]),
+    "jb_serial_scratch_forget": (_i32, [_c_void_p]),
+    "jb_stepper_error": (_i32, []),
+    "jb_stepper_prof": (_i32, [_c_void_p]),
+    "jb_hot_detect": (_i32, [_c_void_p, _i32, _c_void_p, _i64, _i32, _i32, _i32, _c_void_p,
+                             _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p]),
+    "jb_linear_classify": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32, _c_void_p,
+                                  _c_void_p]),
+    "jb_scale": (_i32, [_c_void_p, _i64, _f32, _c_void_p]),
+    "jb_regression_train_m": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
+                                     _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _f32, _f32,
+                                     _i32, _c_void_p]),
+    "jb_regression_estimate": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
+                                      _c_void_p]),
+    "jb_signature": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _i32, _u64, _i32, _c_void_p,
+                            _c_void_p, _c_void_p]),
+    "jb_hamming_scan": (_i32, [_c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64,
+                               _i32, _i32, _i32, _c_void_p, _c_void_p]),
+    "jb_sparse_scan": (_i32, [_c_void_p, _c_void_p, _i32, _f32, _c_void_p, _c_void_p, _c_void_p,
+                              _c_void_p, _c_void_p, _i64, _i32, _c_void_p, _c_void_p]),
+    "jb_mix_apply": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i64, _f32, _c_void_p]),
+    "jb_classify_direct": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32, _c_void_p,
+                                  _c_void_p, _c_void_p]),
+    "jb_topk": (_i32, [_i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64,
+                       _i32, _i32, _i32, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
+                       _c_void_p, _c_void_p]),
+    "jb_nn_reduce": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _c_void_p, _i32, _i32, _f32,
+                            _c_void_p, _c_void_p, _c_void_p]),
+    "jb_topk_blocks": (_i32, [_i64, _i32]),
+    "jb_topk_mq_stats": (_i32, [_c_void_p]),
+    "jb_topk_direct_scratch": (_i64, [_i32]),
+    "jb_topk_scratch_init": (_i32, [_c_void_p, _c_void_p]),
+    "jb_topk_set_prof": (None, [_c_void_p]),
+    "jb_topk_direct_query_path": (_i32, [_c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
+                                         _c_void_p, _i64, _i32, _i32, _i32, _i32, _c_void_p,
+                                         _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
+                                         _c_void_p]),
+    "jb_topk_scores_direct_path": (_i32, [_c_void_p, _i32, _i32, _i64, _i32, _c_void_p, _c_void_p,
+                                          _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p]),
+    "jb_lsh_query_direct": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _i32, _u64, _i32, _i32,
+                                   _c_void_p, _c_void_p, _c_void_p, _i64, _i32, _c_void_p,
+                                   _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                   _c_void_p]),
+    "jb_lsh_set_rows_direct": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32, _u64,
+                                      _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "jb_pool_query_direct": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
+                                    _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p,
+                                    _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
+                                    _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "jb_topk_scores_direct": (_i32, [_c_void_p, _i32, _i32, _i64, _i32, _c_void_p, _c_void_p,
+                                     _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "jb_topk_direct_query": (_i32, [_c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p,
+                                    _i64, _i32, _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
+                                    _c_void_p, _c_void_p, _c_void_p]),
+    "jb_diag_empty": (_i32, [_c_void_p, _i32, _c_void_p]),
+    "jb_scan_train": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
+                             _i32, _c_void_p, _i32, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
+                             _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _i64,
+                             _c_void_p, _c_void_p]),
+    "jb_scan_train_profile": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p,
+                                     _c_void_p, _i32, _c_void_p, _i32, _i32, _i32, _c_void_p,
+                                     _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
+                                     _c_void_p, _c_void_p, _c_void_p]),
+    "jb_pool_scan": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32,
+                            _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p,
+                            _i32, _i32, _c_void_p, _c_void_p]),
+    "jb_pool_append": (_i32, [_c_void_p, _i32, _i64, _i64, _c_void_p, _c_void_p, _c_void_p,
+                              _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "jb_lof_add": (_i32, [_i32, _c_void_p, _c_void_p, _i32, _i32, _i32, _i64, _c_void_p, _c_void_p,
+                          _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                          _c_void_p, _i32, _c_void_p]),
+    "jb_lof_add_many": (_i32, [_i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32,
+                               _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                               _c_void_p, _c_void_p, _c_void_p, _c_void_p, _u32, _c_void_p,
+                               _c_void_p, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32,
+                               _c_void_p]),
+    "jb_lof_mark": (_i32, [_i64, _i32, _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
+                           _c_void_p]),
+    "jb_lof_set_lists": (_i32, [_i32, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _i32, _c_void_p,
+                                _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                _c_void_p]),
+    "jb_lof_score": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
+                            _c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32, _c_void_p]),
+    "jb_fvw_count": (_i32, [_c_void_p, _i64, _c_void_p, _c_void_p, _i32, _c_void_p, _i32, _c_void_p,
+                            _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "jb_fvw_emit": (_i32, [_c_void_p, _i64, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _i32,
+                           _c_void_p, _i32, _c_void_p, _u64, _c_void_p, _c_void_p, _c_void_p,
+                           _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "jb_fvw_comb": (_i32, [_c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                           _i32, _c_void_p, _u64, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                           _c_void_p]),
+    "jb_fvw_name_bytes": (_i64, []),
+    "jb_kmeanspp": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
+                           _c_void_p, _c_void_p, _c_void_p]),
+    "jb_gmm_em": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
+                         _i32, _c_void_p, _c_void_p]),
+    "jb_lloyd": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _f32, _f32,
+                        _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "jb_sqdist_mfma": (_i32, [_c_void_p, _i64, _c_void_p, _i32, _i32, _c_void_p, _c_void_p,
+                              _c_void_p, _c_void_p]),
+    "jb_argmin_rows": (_i32, [_c_void_p, _i64, _i32, _c_void_p, _c_void_p]),
+    "jb_dbscan": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _f32, _f32, _c_void_p,
+                         _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "jb_host_alloc": (_c_void_p, [_i64]),
+    "jb_host_free": (_i32, [_c_void_p]),
 }
 
 DBSCAN_MAX_N = 65536        # csrc/hip/dbscan.hip kDbscanMaxN: the bitmap is n * n / 8 bytes
@@ -646,8 +659,7 @@ def _fn(name: str):
     if f is None:
         lib = hip_lib()
         raw = getattr(lib, name)
-        raw.argtypes = _SIGS[name]
-        raw.restype = ctypes.c_int64 if name.endswith(("_bytes", "_create")) else ctypes.c_int
+        raw.restype, raw.argtypes = _SIGS[name]
         tag = "hip." + name[3:]
 
         tx = _roctx()
@@ -985,41 +997,35 @@ def regression_train(row_ptr, fidx, fval, targets, stream_ptr, nstreams: int, W,
     AROW and NHERD take the precision table ``P`` (like W) and, for samples of
     more than 256 slots, ``slot_scratch`` (float32, as long as fval; without
     it the widths are checked here, which costs a device synchronisation).
-    PA takes the entry it always took."""
+    The library launches PA's own kernel for PA."""
+    from ..models.linear_oracle import METHOD_IDS, USES_COVARIANCE
     _dev(W, torch.float32, "W")
     _dev(stats, torch.float32, "stats")
     _dev(targets, torch.float32, "targets")
     if W.dim() != 1 or stats.numel() < 3 or stream_ptr.numel() < nstreams + 1:
         raise ValueError("regression_train: bad operand shapes")
-    if method != "PA":
-        from ..models.linear_oracle import METHOD_IDS, USES_COVARIANCE
-        if method not in METHOD_IDS:
-            raise ValueError(f"regression_train: unknown method {method}")
-        mid = METHOD_IDS[method]
-        if mid in USES_COVARIANCE:
-            if P is None:
-                raise ValueError(f"regression_train: {method} needs the precision table P")
-            _dev(P, torch.float32, "P")
-            if P.shape != W.shape:
-                raise ValueError("regression_train: P must have the shape of W")
-            if slot_scratch is not None:
-                _dev(slot_scratch, torch.float32, "slot_scratch")
-                if slot_scratch.numel() < fval.numel():
-                    raise ValueError("regression_train: slot_scratch is shorter than fval")
-            elif row_ptr.numel() > 1 and int((row_ptr[1:] - row_ptr[:-1]).max()) > 256:
-                raise ValueError("regression_train: samples of more than 256 slots need slot_scratch")
-        else:
-            P = slot_scratch = None
-        rc = _fn("jb_regression_train_m")(_p(row_ptr), _p(fidx), _p(fval), _p(targets),
-                                          _p(stream_ptr), nstreams, _p(W), _p(P), _p(stats),
-                                          _p(slot_scratch), mid, float(C), float(eps),
-                                          1 if concurrent else 0, _stream())
-        _check(rc, "jb_regression_train_m")
-        return
-    rc = _fn("jb_regression_train")(_p(row_ptr), _p(fidx), _p(fval), _p(targets), _p(stream_ptr),
-                                    nstreams, _p(W), _p(stats), float(C), float(eps),
-                                    1 if concurrent else 0, _stream())
-    _check(rc, "jb_regression_train")
+    if method not in METHOD_IDS:
+        raise ValueError(f"regression_train: unknown method {method}")
+    mid = METHOD_IDS[method]
+    if mid in USES_COVARIANCE:
+        if P is None:
+            raise ValueError(f"regression_train: {method} needs the precision table P")
+        _dev(P, torch.float32, "P")
+        if P.shape != W.shape:
+            raise ValueError("regression_train: P must have the shape of W")
+        if slot_scratch is not None:
+            _dev(slot_scratch, torch.float32, "slot_scratch")
+            if slot_scratch.numel() < fval.numel():
+                raise ValueError("regression_train: slot_scratch is shorter than fval")
+        elif row_ptr.numel() > 1 and int((row_ptr[1:] - row_ptr[:-1]).max()) > 256:
+            raise ValueError("regression_train: samples of more than 256 slots need slot_scratch")
+    else:
+        P = slot_scratch = None
+    rc = _fn("jb_regression_train_m")(_p(row_ptr), _p(fidx), _p(fval), _p(targets),
+                                      _p(stream_ptr), nstreams, _p(W), _p(P), _p(stats),
+                                      _p(slot_scratch), mid, float(C), float(eps),
+                                      1 if concurrent else 0, _stream())
+    _check(rc, "jb_regression_train_m")
 
 
 def regression_estimate(row_ptr, fidx, fval, n: int, W, out) -> None:
@@ -1122,13 +1128,9 @@ class HostBuffer:
     write into directly; exposed to the host as a numpy array."""
 
     def __init__(self, nbytes: int):
-        lib = hip_lib()
-        lib.jb_host_alloc.restype = ctypes.c_void_p
-        lib.jb_host_alloc.argtypes = [_i64]
-        lib.jb_host_free.argtypes = [_c_void_p]
-        self._lib = lib
+        self._free = _fn("jb_host_free")
         self.nbytes = int(nbytes)
-        self.ptr = lib.jb_host_alloc(self.nbytes)
+        self.ptr = _fn("jb_host_alloc")(self.nbytes)
         if not self.ptr:
             raise MemoryError(f"hipHostMalloc({nbytes}) failed")
         ctypes.memset(self.ptr, 0, self.nbytes)
@@ -1143,7 +1145,7 @@ class HostBuffer:
 
     def __del__(self):
         if getattr(self, "ptr", None):
-            self._lib.jb_host_free(self.ptr)
+            self._free(self.ptr)
             self.ptr = None
 
 

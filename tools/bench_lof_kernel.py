@@ -8,7 +8,6 @@ edits, write-back, score loads, score, host copy).
 Usage: python tools/bench_lof_kernel.py [--rows 100000] [--batch 32] [--batches 200]
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -56,11 +55,7 @@ def main():
     prof = torch.zeros(16, dtype=torch.int64, device=d)
     stage = hip.HostBuffer(4 * (2 * 64 + 2 * 64 * 128))
     out = hip.HostBuffer(4 * 64 * stride_out)
-    lib = hip.hip_lib()
-    f = lib.jb_lof_add_many
-    P, I, U = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32
-    f.argtypes = [I, P, P, P, P, I, I, I, P, P, P, P, P, P, P, P, P, P, U, P, P, P, I, I, P, P, I, P]
-    f.restype = I
+    f = hip._fn("jb_lof_add_many")
     rng = np.random.default_rng(1)
     hps = stage.view(np.int32, 64)
     hnc = stage.view(np.int32, 64, 4 * 64)

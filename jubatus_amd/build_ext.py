@@ -85,6 +85,7 @@ def build_native(force: bool = False, nproc: int = 8) -> str:
 def build_hip(force: bool = False, nproc: int = 8) -> str:
     srcs = sorted(glob.glob(os.path.join(CSRC, "hip", "*.hip")))
     hdrs = sorted(glob.glob(os.path.join(CSRC, "hip", "*.h*")))
+    hdrs.append(os.path.join(CSRC, "native", "jb_fv_layout.hpp"))   # included by hip/jb_fv.hpp
     if not force and not _newer(HIP_SO, srcs + hdrs):
         return HIP_SO
     os.makedirs(BUILD, exist_ok=True)

@@ -7,6 +7,7 @@
 // the host converter (csrc/native/jb_converter.cpp):
 //     string rule  : "<key>$<value>@<type>#<sample_weight>/<global_weight>"
 //     num rule     : "<key>@num"  (value)   |  "<key>@log" (log(max(1,value)))
+//     num filters  : "<key><suffix>..@num" (f(value)): derived num rule rows, jb_fv.hpp
 // The feature index is hash_to_index(FNV1a64(name), hash_max_size).
 //
 // Design (MI355X): the raw request bytes (as received by the RPC layer) are

@@ -3,6 +3,13 @@
 // feature order, same hash. Used by the low-latency classify path, where a
 // request of a few datums is hashed on the CPU (~0.3 us) and its (idx, val)
 // pairs travel to the GPU inside the kernel arguments (csrc/hip/classify_direct.hip).
+//
+// Num filters with a built-in method are derived rows of the num rule table
+// (layout and example: csrc/hip/jb_fv.hpp): the slot sequence is the device's,
+// slot by slot. Values are bit-identical to the device's for add,
+// linear_normalization and gaussian_normalization; sigmoid_normalization goes
+// through libm's exp here and the device's own there, so the fp32 values may
+// differ by 1 ulp.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -10,6 +17,7 @@
 
 #include <vector>
 
+#include "jb_fv_layout.hpp"
 #include "jb_hash.hpp"
 #include "jb_msgpack.hpp"
 
@@ -20,6 +28,29 @@ struct HostRule {        // byte layout of jb::GpuRule / gpu_path._RULE
   float weight;
   int32_t pad;
 };
+
+// ---- num filters as derived num rows: layout in jb_fv_layout.hpp
+// One filter in fp64: the expressions of converter.py and jb_hostfv_wide.hpp.
+// add, linear and gaussian are bit-identical to the device's; sigmoid uses
+// libm's exp where the device uses its own, so the fp32 results may differ by
+// 1 ulp (batched classify hashes on the device, classify_direct here). A finite
+// -g(x - b) above ~709.78 gives 0.0 (exp = inf) on both, as the reference's
+// C++ does, where Python's math.exp raises OverflowError.
+inline double filter_apply(int method, double a, double b, bool truncate, double x) {
+  switch (method) {
+    case kFilterAdd: return x + a;
+    case kFilterLinear: {
+      double y = (x - a) / (b - a);
+      if (truncate) {          // std::min(1.0, std::max(0.0, y)): NaN -> 0.0
+        y = (0.0 < y) ? y : 0.0;
+        y = (y < 1.0) ? y : 1.0;
+      }
+      return y;
+    }
+    case kFilterGauss: return (x - a) / b;
+    default: return 1.0 / (1.0 + exp(-a * (x - b)));
+  }
+}
 
 class HostFvHasher {
  public:
@@ -63,6 +94,43 @@ class HostFvHasher {
     return memcmp(base, m, mn) == 0;
   }
 
+  // the matcher over key || ext (jb_fv.hpp ext_key_matches)
+  static bool match_ext(int kind, const uint8_t* m, uint32_t mn, const uint8_t* k, uint32_t kn,
+                        const uint8_t* e, uint32_t en) {
+    if (kind == 0) return true;
+    const uint32_t tn = kn + en;
+    if (kind == 3 && tn != mn) return false;
+    if (tn < mn) return false;
+    const uint32_t start = kind == 2 ? tn - mn : 0;
+    for (uint32_t i = 0; i < mn; ++i) {
+      const uint32_t p = start + i;
+      if ((p < kn ? k[p] : e[p - kn]) != m[i]) return false;
+    }
+    return true;
+  }
+
+  // a derived row on one value (jb_fv.hpp chain_matches); the programme is
+  // read byte-wise, std::vector gives it no alignment
+  bool chain(const HostRule& r, const uint8_t* k, uint32_t kn, double* y) const {
+    const uint8_t* pg = blob_.data() + r.pad;
+    int32_t n_steps, ext_len;
+    memcpy(&n_steps, pg, 4);
+    memcpy(&ext_len, pg + 4, 4);
+    const uint8_t* ext = blob_.data() + r.suffix_off;
+    double v = *y;
+    for (int32_t j = 0; j < n_steps; ++j) {
+      FilterStep s;
+      memcpy(&s, pg + 8 + sizeof(FilterStep) * (size_t)j, sizeof s);
+      if (!match_ext(s.match_kind, blob_.data() + s.match_off, (uint32_t)s.match_len, k, kn, ext,
+                     (uint32_t)s.ext_len))
+        return false;
+      v = filter_apply(s.method, s.a, s.b, s.truncate != 0, v);
+    }
+    *y = v;
+    return match_ext(r.match_kind, blob_.data() + r.match_off, (uint32_t)r.match_len, k, kn, ext,
+                     (uint32_t)ext_len);
+  }
+
   int datum(Cursor& c, int32_t* idx, float* val, int64_t max_slots, int64_t* slots) const {
     uint32_t top, ns, nn;
     if (!c.array(&top) || top < 2) return 1;
@@ -93,10 +161,11 @@ class HostFvHasher {
       const uint64_t hk = fnv_bytes(kFnvOffset, k, kn);
       for (const HostRule& r : n_) {
         if (*slots >= max_slots) return 2;
-        if (match(r, k, kn)) {
+        double y = x;
+        if ((r.value_kind & kDerivedRow) ? chain(r, k, kn, &y) : match(r, k, kn)) {
           idx[*slots] = (int32_t)hash_to_index(fnv_bytes(hk, blob_.data() + r.suffix_off,
                                                          (size_t)r.suffix_len), H_);
-          val[*slots] = r.value_kind == 1 ? logf(fmaxf(1.f, (float)x)) : (float)x;
+          val[*slots] = (r.value_kind & 1) ? logf(fmaxf(1.f, (float)y)) : (float)y;
         } else {
           idx[*slots] = -1;
           val[*slots] = 0.f;

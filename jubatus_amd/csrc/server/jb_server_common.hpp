@@ -245,11 +245,168 @@ inline bool nonempty_list(const Value& conv, const char* key) {
   return v && v->kind == Value::ARR && !v->a.empty();
 }
 
+inline double as_double(const Value* v, double dflt, bool* ok) {
+  if (!v) { *ok = false; return dflt; }
+  if (v->is_num()) return v->num();
+  if (v->is_str()) {
+    char* end = nullptr;
+    const double d = strtod(v->s.c_str(), &end);
+    if (end && *end == 0 && !v->s.empty()) return d;
+  }
+  *ok = false;
+  return dflt;
+}
+
+// One entry of num_filter_types with a built-in method (converter.py): its
+// kind (jb::kFilterAdd .. kFilterSigmoid, the values of WideExt's num filter
+// kinds) and parameters. -1 with a reason on bad parameters, -2 when the
+// method is not a built-in one (`why` untouched). Shared by the fixed-slot
+// tables (build_rules) and the wide converter's WideExt (jb_wide_rules.hpp).
+struct NumFilterType {
+  int kind = -1;
+  double a = 0, b = 0;
+  bool trunc = true;
+};
+inline int parse_num_filter_type(const std::string& name, const Value& t, NumFilterType* f,
+                                 std::string* why) {
+  const std::string m = t.str_or("method", "");
+  bool ok = true;
+  if (m == "add") {
+    f->kind = jb::kFilterAdd;
+    f->a = as_double(t.get("value"), 0, &ok);
+  } else if (m == "linear_normalization") {
+    f->kind = jb::kFilterLinear;
+    f->a = as_double(t.get("min"), 0, &ok);
+    f->b = as_double(t.get("max"), 0, &ok);
+    // converter.py: str(p.get("truncate", "true")).lower() != "false" - a
+    // JSON false switches it off as the string "false" does
+    const Value* tv = t.get("truncate");
+    if (tv && tv->kind == Value::BOOL) {
+      f->trunc = tv->b;
+    } else {
+      std::string tr = t.str_or("truncate", "true");
+      for (auto& ch : tr) ch = (char)tolower(ch);
+      f->trunc = tr != "false";
+    }
+    if (ok && !(f->b > f->a)) { *why = "linear_normalization: max must exceed min"; return -1; }
+  } else if (m == "gaussian_normalization") {
+    f->kind = jb::kFilterGauss;
+    f->a = as_double(t.get("average"), 0, &ok);
+    f->b = as_double(t.get("standard_deviation"), 0, &ok);
+    if (ok && !(f->b > 0)) { *why = "gaussian_normalization: standard_deviation must be > 0"; return -1; }
+  } else if (m == "sigmoid_normalization") {
+    f->kind = jb::kFilterSigmoid;
+    f->a = as_double(t.get("gain"), 0, &ok);
+    f->b = as_double(t.get("bias"), 0, &ok);
+  } else {
+    return -2;
+  }
+  if (!ok) { *why = "num filter " + name + ": parameters"; return -1; }
+  return 0;
+}
+
+inline bool bytes_match(int kind, const std::string& arg, const std::string& key) {
+  if (kind == 0) return true;
+  if (kind == 3) return key == arg;
+  if (key.size() < arg.size()) return false;
+  return key.compare(kind == 2 ? key.size() - arg.size() : 0, arg.size(), arg) == 0;
+}
+
+// the num filter rules as derived rows of the num rule table
+// (fv_converter/gpu_path.py _filter_steps, _filter_chains and the second half
+// of GpuRuleTable, byte for byte; layout: csrc/hip/jb_fv.hpp)
+inline bool build_filter_rows(const Value& conv, Rules* r, std::string* why) {
+  struct Step { int kind; std::string arg, suffix; NumFilterType t; int32_t off = 0; };
+  std::vector<Step> steps;
+  const Value* types = conv.get("num_filter_types");
+  for (const Value& x : conv.get("num_filter_rules")->a) {
+    const std::string type = x.str_or("type", "");
+    const Value* t = types && types->kind == Value::MAP ? types->get(type) : nullptr;
+    if (!t) { *why = "unknown num filter type: " + type; return false; }
+    Step s;
+    const int rc = parse_num_filter_type(type, *t, &s.t, why);
+    if (rc == -2) { *why = "num filter method " + t->str_or("method", "") + " needs the host converter"; return false; }
+    if (rc) return false;
+    s.kind = matcher_kind(x.str_or("key", ""), &s.arg);
+    if (s.kind < 0) { *why = "regex key matcher"; return false; }
+    s.suffix = x.str_or("suffix", "");
+    steps.push_back(s);
+  }
+  struct Chain { std::vector<int> idx; bool known; std::string key, ext; };
+  std::vector<Chain> chains{{{}, false, "", ""}};
+  for (size_t f = 0; f < steps.size(); ++f) {
+    const Step& s = steps[f];
+    const size_t n0 = chains.size();
+    for (size_t c = 0; c < n0; ++c) {
+      Chain nc = chains[c];
+      if (nc.known) {
+        if (!bytes_match(s.kind, s.arg, nc.key + nc.ext)) continue;
+      } else if (s.kind == 3) {
+        if (s.arg.size() < nc.ext.size() ||
+            s.arg.compare(s.arg.size() - nc.ext.size(), nc.ext.size(), nc.ext) != 0)
+          continue;
+        nc.known = true;
+        nc.key = s.arg.substr(0, s.arg.size() - nc.ext.size());
+      }
+      nc.idx.push_back((int)f);
+      nc.ext += s.suffix;
+      chains.push_back(nc);
+      if ((int)chains.size() - 1 > jb::kMaxFilterChains) {
+        *why = "num_filter_rules make more than " + std::to_string(jb::kMaxFilterChains) +
+               " filter chains: they need the host converter";
+        return false;
+      }
+    }
+  }
+  for (Step& s : steps) {
+    s.off = (int32_t)r->blob.size();
+    r->blob += s.arg;
+  }
+  std::vector<int32_t> progs;
+  for (size_t c = 1; c < chains.size(); ++c) {
+    r->blob.append((8 - r->blob.size() % 8) % 8, '\0');
+    progs.push_back((int32_t)r->blob.size());
+    std::string prog;
+    int32_t ext = 0;
+    for (int f : chains[c].idx) {
+      const Step& s = steps[(size_t)f];
+      jb::FilterStep fs{};
+      fs.match_kind = s.kind;
+      fs.match_off = s.off;
+      fs.match_len = (int32_t)s.arg.size();
+      fs.ext_len = ext;
+      fs.method = s.t.kind;
+      fs.truncate = s.t.kind == jb::kFilterLinear && s.t.trunc;
+      fs.a = s.t.a;
+      fs.b = s.t.b;
+      prog.append((const char*)&fs, sizeof fs);
+      ext += (int32_t)s.suffix.size();
+    }
+    const int32_t head[2] = {(int32_t)chains[c].idx.size(), ext};
+    r->blob.append((const char*)head, sizeof head);
+    r->blob += prog;
+  }
+  const size_t n_base = r->n.size();
+  for (size_t c = 1; c < chains.size(); ++c) {
+    for (size_t b = 0; b < n_base; ++b) {
+      jb::HostRule h = r->n[b];
+      const std::string tail = r->blob.substr((size_t)h.suffix_off, (size_t)h.suffix_len);
+      h.suffix_off = (int32_t)r->blob.size();
+      h.suffix_len = (int32_t)(chains[c].ext.size() + tail.size());
+      r->blob += chains[c].ext + tail;
+      h.value_kind |= jb::kDerivedRow;
+      h.pad = progs[c - 1];
+      r->n.push_back(h);
+    }
+  }
+  return true;
+}
+
 // the fixed-slot GPU converter (fv_converter/gpu_path.py fast_eligible +
 // GpuRuleTable): false with a reason when the config needs the host converter
 inline bool build_rules(const Value& conv, Rules* r, std::string* why) {
   if (conv.kind != Value::MAP) { *why = "converter is not an object"; return false; }
-  for (const char* k : {"string_filter_rules", "num_filter_rules", "binary_rules", "combination_rules"})
+  for (const char* k : {"string_filter_rules", "binary_rules", "combination_rules"})
     if (nonempty_list(conv, k)) { *why = std::string(k) + " need the host converter"; return false; }
   const Value* st = conv.get("string_types");
   const Value* nt = conv.get("num_types");
@@ -301,7 +458,49 @@ inline bool build_rules(const Value& conv, Rules* r, std::string* why) {
       r->n.push_back(h);
     }
   }
+  if (nonempty_list(conv, "num_filter_rules") && !build_filter_rows(conv, r, why)) {
+    r->s.clear();   // as before filters were served here: a refused filter config leaves no rows
+    r->n.clear();
+    r->blob.clear();
+    return false;
+  }
   return true;
+}
+
+// --native-check with JUBATUS_NATIVE_CHECK_RULES set: one more line with the
+// fixed-slot tables build_rules packs from the config's converter, as hex
+// ("fixed-slot rules: H <string rows> <num rows> <blob>", "-" for an empty
+// field), or the reason it refuses the config. The tests compare it with
+// gpu_path.GpuRuleTable byte for byte.
+inline void print_fixed_slot_rules(const std::string& config_text) {
+  Rules r;
+  std::string why;
+  bool ok = false;
+  try {
+    const Value cfg = jb::val::parse_json(config_text);
+    const Value* conv = cfg.get("converter");
+    const Value empty = jb::val::parse_json("{}");
+    ok = build_rules(conv ? *conv : empty, &r, &why);
+  } catch (const std::exception& e) {
+    why = e.what();
+  }
+  if (!ok) {
+    printf("fixed-slot rules: no: %s\n", why.c_str());
+    return;
+  }
+  auto hex = [](const void* p, size_t n) {
+    static const char* d = "0123456789abcdef";
+    std::string o;
+    for (size_t i = 0; i < n; ++i) {
+      const uint8_t b = ((const uint8_t*)p)[i];
+      o += d[b >> 4];
+      o += d[b & 15];
+    }
+    return o.empty() ? std::string("-") : o;
+  };
+  printf("fixed-slot rules: %llu %s %s %s\n", (unsigned long long)r.H,
+         hex(r.s.data(), r.s.size() * sizeof(jb::HostRule)).c_str(),
+         hex(r.n.data(), r.n.size() * sizeof(jb::HostRule)).c_str(), hex(r.blob.data(), r.blob.size()).c_str());
 }
 
 inline bool read_file(const std::string& path, std::string* out) {
@@ -709,6 +908,7 @@ int startup(int argc, char** argv, Args* a, std::string* text, Check check, bool
   if (a->native_check) {   // the config check alone (tests, operators): no GPU, no exec
     const bool ok = check(*text, &why);
     printf("%s\n", ok ? "native" : ("python: " + why).c_str());
+    if (getenv("JUBATUS_NATIVE_CHECK_RULES")) print_fixed_slot_rules(*text);
     return 0;
   }
   if (!check(*text, &why)) exec_python(argc, argv, why.c_str());

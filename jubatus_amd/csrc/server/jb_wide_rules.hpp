@@ -77,17 +77,7 @@ inline int load_plugin(WideExt* ext, const Value& t, int kind, std::string* why)
   }
 }
 
-inline double as_double(const Value* v, double dflt, bool* ok) {
-  if (!v) { *ok = false; return dflt; }
-  if (v->is_num()) return v->num();
-  if (v->is_str()) {
-    char* end = nullptr;
-    const double d = strtod(v->s.c_str(), &end);
-    if (end && *end == 0 && !v->s.empty()) return d;
-  }
-  *ok = false;
-  return dflt;
-}
+using jb::srv::as_double;   // jb_server_common.hpp
 
 // fv_converter/gpu_path.py wide_eligible + WideRuleTable; with `ext` also the
 // "dynamic" plug-in types, the filter rules (plug-in string filters; add /
@@ -141,38 +131,25 @@ inline bool build_wide_rules(const Value& conv, std::vector<HostRule>* s, std::v
     if (const Value* t = conv.get("num_filter_types")) {
       if (t->kind != Value::MAP) { *why = "num_filter_types"; return false; }
       for (const auto& kv : t->o) {
-        const std::string m = kv.second.str_or("method", "");
+        // the built-in methods: one parser with the fixed-slot tables
+        // (jb_server_common.hpp parse_num_filter_type; kinds kAdd .. kSigmoid)
         WideExt::Filter f;
-        bool ok = true;
-        if (m == "add") {
-          f.kind = WideExt::kAdd;
-          f.a = as_double(kv.second.get("value"), 0, &ok);
-        } else if (m == "linear_normalization") {
-          f.kind = WideExt::kLinear;
-          f.a = as_double(kv.second.get("min"), 0, &ok);
-          f.b = as_double(kv.second.get("max"), 0, &ok);
-          std::string tr = kv.second.str_or("truncate", "true");
-          for (auto& ch : tr) ch = (char)tolower(ch);
-          f.trunc = tr != "false";
-          if (ok && !(f.b > f.a)) { *why = "linear_normalization: max must exceed min"; return false; }
-        } else if (m == "gaussian_normalization") {
-          f.kind = WideExt::kGauss;
-          f.a = as_double(kv.second.get("average"), 0, &ok);
-          f.b = as_double(kv.second.get("standard_deviation"), 0, &ok);
-          if (ok && !(f.b > 0)) { *why = "gaussian_normalization: standard_deviation must be > 0"; return false; }
-        } else if (m == "sigmoid_normalization") {
-          f.kind = WideExt::kSigmoid;
-          f.a = as_double(kv.second.get("gain"), 0, &ok);
-          f.b = as_double(kv.second.get("bias"), 0, &ok);
-        } else if (m == "dynamic") {
+        jb::srv::NumFilterType bt;
+        const int rc = jb::srv::parse_num_filter_type(kv.first, kv.second, &bt, why);
+        if (rc == -1) return false;
+        if (rc == 0) {
+          f.kind = bt.kind;
+          f.a = bt.a;
+          f.b = bt.b;
+          f.trunc = bt.trunc;
+        } else if (kv.second.str_or("method", "") == "dynamic") {
           f.kind = WideExt::kPlug;
           f.plug = load_plugin(ext.get(), kv.second, plug::kNumFilter, why);
           if (f.plug < 0) return false;
         } else {
-          *why = "num filter method " + m;
+          *why = "num filter method " + kv.second.str_or("method", "");
           return false;
         }
-        if (!ok) { *why = "num filter " + kv.first + ": parameters"; return false; }
         nft[kv.first] = f;
       }
     }

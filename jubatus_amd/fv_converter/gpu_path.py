@@ -4,15 +4,30 @@ Decides whether a converter config runs on the GPU and packs its rules
 into the device rule tables.
 
 * fast path (``fast_eligible``, csrc/hip/fv_hash.hip + scan.hip, one slot
-  per (value, rule)): no filters, no binary or combination rules; every
-  string rule is of built-in type ``str`` with global weight ``bin``; every
-  num rule is ``num`` or ``log``; key matchers ``*``, prefix, suffix, exact;
+  per (value, rule row)): no string filters, no binary or combination rules;
+  every string rule is of built-in type ``str`` with global weight ``bin``;
+  every num rule is ``num`` or ``log``; key matchers ``*``, prefix, suffix,
+  exact. Num filters with a built-in method (``add``,
+  ``linear_normalization``, ``gaussian_normalization``,
+  ``sigmoid_normalization``) run there too: every chain of filters
+  ``f1 < f2 < ...`` that can fire, followed by a num rule, is one more row of
+  the num rule table (layout: csrc/hip/jb_fv.hpp), up to
+  ``MAX_FILTER_CHAINS`` chains. For example ::
+
+      "num_filter_types": {"z": {"method": "gaussian_normalization",
+                                 "average": 170, "standard_deviation": 8}},
+      "num_filter_rules": [{"key": "height", "type": "z", "suffix": "_z"}],
+      "num_rules":        [{"key": "*", "type": "num"}]
+
+  packs the base row (``*``, ``@num``) and the derived row of chain ``(0,)``
+  with suffix ``_z@num``: two slots per num value;
 * wide rule set (``wide_eligible``, csrc/hip/fv_wide.hip and the native host
   twin csrc/native/jb_hostfv_wide.hpp): adds the ``space`` / ``ngram``
   splitters, tf / log_tf with idf / bm25 global weights and add / mul
-  combinations.
+  combinations; no filters on the device (natively WideExt runs them).
 
-``gpu_eligible`` is either; regex matchers, filters and plug-ins keep the
+``gpu_eligible`` is either; regex matchers, string filters, plug-in
+("dynamic") filters, filter configs above the chain cap and plug-ins keep the
 host converter.
 """
 from __future__ import annotations
@@ -28,10 +43,76 @@ _RULE = struct.Struct("<iiiiiifi")  # mirrors jb::GpuRule
 _KIND = {"all": 0, "prefix": 1, "suffix": 2, "exact": 3}
 
 
+# ---- num filters as derived num rows (csrc/hip/jb_fv.hpp, csrc/native/jb_hostfv.hpp)
+# csrc/native/jb_fv_layout.hpp kMaxFilterChains. The device stages the rule blob
+# in LDS up to 1024 bytes (fv_hash.hip kBlobCap); with many chains (seven and one
+# rule: 0.6 KB, fifteen: 1.4 KB) the blob exceeds that and the kernel reads it from global
+# memory instead: correct and tested, its cost not measured.
+MAX_FILTER_CHAINS = 16
+_DERIVED_ROW = 0x100            # kDerivedRow: value_kind bit of a filter-chain row
+_STEP = struct.Struct("<iiiiiidd")   # mirrors jb::FilterStep
+_METHOD = {"add": 0, "linear_normalization": 1, "gaussian_normalization": 2,
+           "sigmoid_normalization": 3}
+
+
+def _filter_steps(conv: DatumToFvConverter):
+    """the num filter rules as (matcher kind, matcher bytes, suffix bytes,
+    method, a, b, truncate), or None when one of them needs the host converter
+    (a plug-in method, a regex key). The parameters are read as converter.py
+    reads them."""
+    types = conv.config.get("num_filter_types") or {}
+    out = []
+    for rule, (m, _, suffix) in zip(conv.config.get("num_filter_rules") or [], conv.num_filters):
+        p = types.get(rule["type"]) or {}
+        method = p.get("method")
+        if method not in _METHOD or m.kind not in _KIND:
+            return None
+        a, b, trunc = 0.0, 0.0, 0
+        if method == "add":
+            a = float(p["value"])
+        elif method == "linear_normalization":
+            a, b = float(p["min"]), float(p["max"])
+            trunc = int(str(p.get("truncate", "true")).lower() != "false")
+        elif method == "gaussian_normalization":
+            a, b = float(p["average"]), float(p["standard_deviation"])
+        else:
+            a, b = float(p["gain"]), float(p["bias"])
+        out.append((_KIND[m.kind], m.arg.encode(), suffix.encode(), _METHOD[method], a, b, trunc))
+    return out
+
+
+def _bytes_match(kind: int, arg: bytes, key: bytes) -> bool:
+    return (kind == 0 or (kind == 1 and key.startswith(arg)) or
+            (kind == 2 and key.endswith(arg)) or (kind == 3 and key == arg))
+
+
+def _filter_chains(steps):
+    """every chain (f1 < f2 < ...) of filter indices that can fire, in the
+    order converter.py _filtered appends the derived values, or None above
+    MAX_FILTER_CHAINS. Pruned: once an exact matcher has fixed the original
+    key, every later step is decided here; an exact matcher whose argument
+    does not end with the suffixes appended so far never matches."""
+    chains = [((), None, b"")]          # (indices, the key if known, suffixes so far)
+    for f, (kind, arg, suffix, *_rest) in enumerate(steps):
+        for idx, known, ext in list(chains):
+            if known is not None:
+                if not _bytes_match(kind, arg, known + ext):
+                    continue
+            elif kind == 3:
+                if not arg.endswith(ext):
+                    continue
+                known = arg[:len(arg) - len(ext)]
+            chains.append((idx + (f,), known, ext + suffix))
+            if len(chains) - 1 > MAX_FILTER_CHAINS:
+                return None
+    return [c[0] for c in chains[1:]]
+
+
 def fast_eligible(conv: DatumToFvConverter) -> bool:
     """the fixed-slot fast path (fv_hash.hip / scan.hip): one slot per
-    (value, rule), constant string weights"""
-    if conv.string_filters or conv.num_filters or conv.binary_rules or conv.combination_rules:
+    (value, rule row), constant string weights; num filters with a built-in
+    method as derived num rows, up to MAX_FILTER_CHAINS chains"""
+    if conv.string_filters or conv.binary_rules or conv.combination_rules:
         return False
     for r in conv.string_rules:
         if r.type_name != "str" or r.splitter is not None or r.gw != "bin":
@@ -41,11 +122,19 @@ def fast_eligible(conv: DatumToFvConverter) -> bool:
     for r in conv.num_rules:
         if r.type_name not in ("num", "log") or r.matcher.kind not in _KIND:
             return False
+    if conv.num_filters:
+        steps = _filter_steps(conv)
+        if steps is None or _filter_chains(steps) is None:
+            return False
     return True
 
 
 class GpuRuleTable:
-    """Packed rule tables: (string rules, num rules, byte blob)."""
+    """Packed rule tables: (string rules, num rules, byte blob). The num
+    rules are the base rows, then one derived row per (filter chain, base
+    row), chain-major; the blob holds the matcher and suffix bytes of the
+    base rows as before, then the filters' matcher bytes, the chain
+    programmes (8-byte aligned) and the derived rows' suffixes."""
 
     def __init__(self, conv: DatumToFvConverter):
         if not fast_eligible(conv):
@@ -63,12 +152,31 @@ class GpuRuleTable:
             so, sl = put(r.suffix.encode())
             w = {"bin": 1.0, "tf": 1.0, "log_tf": math.log(2.0)}[r.sw]
             srows.append(_RULE.pack(_KIND[r.matcher.kind], mo, ml, so, sl, 0, w, 0))
-        nrows = []
+        nrows, base = [], []
         for r in conv.num_rules:
             mo, ml = put(r.matcher.arg.encode())
             so, sl = put(f"@{r.type_name}".encode())
-            nrows.append(_RULE.pack(_KIND[r.matcher.kind], mo, ml, so, sl,
-                                    1 if r.type_name == "log" else 0, 0.0, 0))
+            vk = 1 if r.type_name == "log" else 0
+            base.append((_KIND[r.matcher.kind], mo, ml, f"@{r.type_name}".encode(), vk))
+            nrows.append(_RULE.pack(_KIND[r.matcher.kind], mo, ml, so, sl, vk, 0.0, 0))
+        if conv.num_filters:
+            steps = _filter_steps(conv)
+            chains = _filter_chains(steps)
+            args = [put(st[1]) for st in steps]
+            progs = []
+            for chain in chains:
+                blob.extend(b"\0" * (-len(blob) % 8))
+                prog, ext = bytearray(), 0
+                for f in chain:
+                    kind, _, suffix, method, a, b, trunc = steps[f]
+                    prog += _STEP.pack(kind, args[f][0], args[f][1], ext, method, trunc, a, b)
+                    ext += len(suffix)
+                progs.append(put(struct.pack("<ii", len(chain), ext) + bytes(prog))[0])
+            for chain, po in zip(chains, progs):
+                ext = b"".join(steps[f][2] for f in chain)
+                for kind, mo, ml, tail, vk in base:
+                    so, sl = put(ext + tail)
+                    nrows.append(_RULE.pack(kind, mo, ml, so, sl, vk | _DERIVED_ROW, 0.0, po))
         self.n_srules = len(srows)
         self.n_nrules = len(nrows)
         self.srules = np.frombuffer(b"".join(srows) or b"\0" * _RULE.size, dtype=np.uint8).copy()
@@ -154,7 +262,8 @@ class WideRuleTable:
 
 
 def gpu_eligible(conv: DatumToFvConverter) -> bool:
-    """the GPU converts this config: the fixed-slot fast path or the wide
-    rule-set kernels (csrc/hip/fv_wide.hip: ngram / space, tf / idf / bm25 with
-    the DF table in HBM, combinations)"""
+    """the GPU converts this config: the fixed-slot fast path (built-in num
+    filters included) or the wide rule-set kernels (csrc/hip/fv_wide.hip:
+    ngram / space, tf / idf / bm25 with the DF table in HBM, combinations; no
+    filters)"""
     return fast_eligible(conv) or wide_eligible(conv)

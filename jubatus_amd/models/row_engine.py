@@ -111,7 +111,8 @@ class RowEngine:
         None: csrc/native/jb_hostfv.hpp for the plain rule set,
         csrc/native/jb_hostfv_wide.hpp for ngram / space splitters, tf /
         idf / bm25 weights (the WeightManager's arrays, updated in place) and
-        combinations. No filters / plug-ins / regex matchers."""
+        combinations. Num filters with a built-in method on the plain rule
+        set only; no string filters / plug-ins / regex matchers."""
         if self._host_hasher is None:
             from ..fv_converter.gpu_path import (GpuRuleTable, WideRuleTable, fast_eligible,
                                                  wide_eligible)

@@ -109,6 +109,7 @@ static int classify_direct_impl(const int32_t* idx, const float* val, const int6
                                 uint32_t* done_host, hipStream_t stream) {
   if (n <= 0) return 0;
   if (n > jb::kDirectMaxSamples || row_ptr[n] - row_ptr[0] > jb::kDirectMaxSlots) return 1;
+  if (LC > kTemplateMaxLC) return 1;   // past the template dispatch: the batch path (linear_chunked.hip)
   jb::DirectArgs a;
   a.n = n;
   const int64_t base = row_ptr[0];

@@ -102,6 +102,22 @@ int jb_scale(float* p, int64_t n, float a, hipStream_t stream);
 int jb_mix_apply(float* w, const float* red, const float* loc, int64_t n, float inv_n,
                  hipStream_t stream);
 
+// linear_chunked.hip
+// The same train / classify with a run-time label capacity: LC any multiple
+// of 256 from 256 to 16384 (anything else is refused before a launch).
+// jb_linear_train / jb_linear_classify route label capacities above 1024
+// here. W: float or (w_bf16 != 0) uint16 bf16 bit patterns. mode: kExact (one
+// stream), kAtomic or kHogwild; waves per stream: 1, 4 or 16, 0 for the
+// library's default (JUBATUS_LABEL_WAVES overrides the default).
+int jb_linear_train_chunked(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
+                            const int32_t* labels, const int64_t* stream_ptr, int nstreams,
+                            void* W, int w_bf16, float* P, const int32_t* active, int LC,
+                            int method, float C, int mode, int waves, unsigned long long* stats,
+                            uint8_t* touched, hipStream_t stream);
+int jb_linear_classify_chunked(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
+                               int n_samples, const void* W, int w_bf16, int LC, float* out,
+                               hipStream_t stream);
+
 // lof.hip
 int jb_lof_mark(int64_t nrows, int k, const int32_t* nb_slot, const int32_t* changed,
                 const int32_t* nchanged, int clear_ok, uint8_t* ok, uint8_t* lrd_ok,

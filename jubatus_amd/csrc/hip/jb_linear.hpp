@@ -173,13 +173,13 @@ __device__ __forceinline__ void argmax_wrong(float& best, int& bl) {
   }
 }
 
-// apply the update of one feature (lane-per-feature form)
-template <int LC, int MODE, typename WT>
-__device__ __forceinline__ void apply_feature(WT* W, float* P, int32_t idx, float x, int y,
-                                              int lstar, bool use_s, int method, float tau,
-                                              float beta, float a, float b, float wy, float wl,
-                                              uint32_t rnd) {
-  const int64_t row = (int64_t)idx * LC;
+// apply the update of one feature whose row starts at element `row`
+// (lane-per-feature form)
+template <int MODE, typename WT>
+__device__ __forceinline__ void apply_row(WT* W, float* P, int64_t row, float x, int y,
+                                          int lstar, bool use_s, int method, float tau,
+                                          float beta, float a, float b, float wy, float wl,
+                                          uint32_t rnd) {
   const float dwy = use_s ? tau * a * x : tau * x;
   const float dwl = use_s ? -tau * b * x : -tau * x;
   if (MODE == kAtomic) {
@@ -197,6 +197,15 @@ __device__ __forceinline__ void apply_feature(WT* W, float* P, int32_t idx, floa
       if (lstar >= 0) P[row + lstar] = 1.f / b + dprec(method, beta, x, b);
     }
   }
+}
+
+// the same with a compile-time label capacity
+template <int LC, int MODE, typename WT>
+__device__ __forceinline__ void apply_feature(WT* W, float* P, int32_t idx, float x, int y,
+                                              int lstar, bool use_s, int method, float tau,
+                                              float beta, float a, float b, float wy, float wl,
+                                              uint32_t rnd) {
+  apply_row<MODE>(W, P, (int64_t)idx * LC, x, y, lstar, use_s, method, tau, beta, a, b, wy, wl, rnd);
 }
 
 // One sample on the direct path: gathers straight from W / P (any feature
@@ -267,6 +276,10 @@ __device__ __forceinline__ bool general_sample(const int32_t* __restrict__ fidx,
 }
 
 }  // namespace jb
+
+// the last label capacity of JB_LC_DISPATCH; larger ones run the run-time-LC
+// kernels of linear_chunked.hip
+constexpr int kTemplateMaxLC = 1024;
 
 // label-capacity template dispatch (LC is a power of two, 8..1024)
 #define JB_LC_DISPATCH(LCV, CALL) \

@@ -868,6 +868,22 @@ static int linear_train_impl(const int64_t* row_ptr, const int32_t* fidx, const 
   if (nstreams <= 0) return 0;
   if (mode == jb::kSerial && nstreams == 1) mode = jb::kExact;
   if (mode == jb::kExact && nstreams > 1) mode = jb::kSerial;   // exact means serial-equivalent
+  // label capacities past the template dispatch: the run-time-LC kernel of
+  // linear_chunked.hip; a kSerial batch runs as one sequential stream (the
+  // route of bf16 tables below), no committer, no hot rows
+  if (LC > kTemplateMaxLC) {
+    if (mode == jb::kSerial) {
+      if (scratch == nullptr || scratch_bytes < 16) return -3;
+      hipLaunchKernelGGL(jb::stream_span_kernel, dim3(1), dim3(64), 0, stream, stream_ptr,
+                         nstreams, (int64_t*)scratch);
+      stream_ptr = (const int64_t*)scratch;
+      nstreams = 1;
+      mode = jb::kExact;
+    }
+    return jb_linear_train_chunked(row_ptr, fidx, fval, labels, stream_ptr, nstreams, W,
+                                   sizeof(WT) == 2, S, active, LC, method, C, mode, 0, stats,
+                                   touched, stream);
+  }
   if (mode == jb::kSerial) {
     if constexpr (sizeof(WT) == 4) {
       // score + ordered commit, then the sequential kernel over what is left
@@ -949,6 +965,9 @@ static int linear_classify_impl(const int64_t* row_ptr, const int32_t* fidx, con
                                 int n_samples, const WT* W, int LC, float* out,
                                 hipStream_t stream) {
   if (n_samples <= 0) return 0;
+  if (LC > kTemplateMaxLC)
+    return jb_linear_classify_chunked(row_ptr, fidx, fval, n_samples, W, sizeof(WT) == 2, LC, out,
+                                      stream);
   const int threads = 256;
   const int blocks = (n_samples * 64 + threads - 1) / threads;
 #define JB_CLS(L)                                                                           \

@@ -788,6 +788,9 @@ extern "C" int64_t jb_serial_scratch_bytes(int64_t n_max) {
 // the scratch a label capacity needs: past 64 labels only the bound
 // committer runs
 extern "C" int64_t jb_serial_scratch_bytes_lc(int64_t n_max, int LC) {
+  // past 1024 labels no committer runs: the batch becomes one stream, whose
+  // span is two int64 (linear.hip, stream_span_kernel)
+  if (LC > kTemplateMaxLC) return 16;
   return LC > 64 ? jb::BoundScratch::bytes(n_max > 0 ? n_max : 1) : jb_serial_scratch_bytes(n_max);
 }
 

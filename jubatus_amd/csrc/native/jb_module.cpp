@@ -427,6 +427,7 @@ PYBIND11_MODULE(_jubatus_native, m) {
       .def("lookup", &jb::LabelTable::lookup)
       .def("remove", &jb::LabelTable::remove)
       .def("clear", &jb::LabelTable::clear)
+      .def("truncate", &jb::LabelTable::truncate)
       .def("size", &jb::LabelTable::size)
       .def("names", &jb::LabelTable::names)
       .def("alive", &jb::LabelTable::alive)

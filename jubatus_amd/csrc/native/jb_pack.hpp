@@ -67,6 +67,19 @@ class LabelTable {
     ids_.clear(); names_.clear(); alive_.clear();
     ++version_;
   }
+  // forget the labels with id >= n (a growth of the tables that was refused:
+  // the labels that asked for it never got a column)
+  void truncate(int n) {
+    std::lock_guard<std::mutex> g(mu_);
+    if (n < 0 || (size_t)n >= names_.size()) return;
+    for (size_t i = (size_t)n; i < names_.size(); ++i) {
+      ids_.erase(names_[i]);
+      counts_[i].store(0);
+    }
+    names_.resize((size_t)n);
+    alive_.resize((size_t)n);
+    ++version_;
+  }
   int size() { std::lock_guard<std::mutex> g(mu_); return (int)names_.size(); }
   std::vector<std::string> names() { std::lock_guard<std::mutex> g(mu_); return names_; }
   std::vector<bool> alive() { std::lock_guard<std::mutex> g(mu_); return alive_; }

@@ -65,7 +65,27 @@
 namespace {
 
 const char* const kMethods[] = {"perceptron", "PA", "PA1", "PA2", "CW", "AROW", "NHERD"};
-const int kLabelCaps[] = {8, 16, 32, 64, 128, 256, 512, 1024};
+// models/classifier.py LABEL_CAPS: up to 1024 the LC-templated kernels run,
+// above it the label-chunked ones (csrc/hip/linear_chunked.hip)
+const int kLabelCaps[] = {8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 16384};
+// csrc/hip/jb_linear.hpp kTemplateMaxLC (models/label_caps.py TEMPLATE_MAX_LC):
+// growing past it is checked against the free memory
+constexpr int kTemplateMaxLC = 1024;
+
+// the tables cannot grow for the labels a request registered: too many
+// labels, or no room for the new tables
+struct GrowthRefused : std::runtime_error {
+  using std::runtime_error::runtime_error;
+};
+
+// the label capacity that holds n labels
+int label_cap_for(size_t n) {
+  for (int c : kLabelCaps)
+    if ((size_t)c >= n) return c;
+  throw GrowthRefused("at most " +
+                           std::to_string(kLabelCaps[sizeof kLabelCaps / sizeof kLabelCaps[0] - 1]) +
+                           " labels are supported");
+}
 constexpr int kUpdateExact = 0, kUpdateAtomic = 1, kUpdateSerial = 3;
 
 // how concurrent train requests of one batch update the model: serial-
@@ -195,6 +215,7 @@ class Classifier : public jb::mix::Mixable {
     if (!r.n.empty()) HIPCHK(hipMemcpy(d_nrules_, r.n.data(), rs * r.n.size(), hipMemcpyHostToDevice));
     if (!r.blob.empty()) HIPCHK(hipMemcpy(d_blob_, r.blob.data(), r.blob.size(), hipMemcpyHostToDevice));
     labels_.clear();
+    labels_kept_ = 0;
     alloc_locked(kLabelCaps[0], true);
   }
 
@@ -393,6 +414,7 @@ class Classifier : public jb::mix::Mixable {
     HIPCHK(hipDeviceSynchronize());
     count_base_.clear();
     labels_.clear();
+    labels_kept_ = 0;
     conv_.clear();
     alloc_locked(kLabelCaps[0], true);
   }
@@ -467,11 +489,8 @@ class Classifier : public jb::mix::Mixable {
     std::lock_guard<std::mutex> g(mu_);
     HIPCHK(hipDeviceSynchronize());
     labels_.clear();
-    int cap = -1;
-    for (int c : kLabelCaps)
-      if ((size_t)c >= std::max<size_t>(1, L)) { cap = c; break; }
-    if (cap < 0) throw std::runtime_error("at most 1024 labels are supported");
-    alloc_locked(cap, true);
+    labels_kept_ = 0;
+    alloc_locked(label_cap_for(std::max<size_t>(1, L)), true);
     for (size_t k = 0; k < L; ++k) {
       labels_.get_or_add(lv->a[k].s.data(), lv->a[k].s.size());
       labels_.set_count((int)k, k < cv->a.size() ? (uint64_t)cv->a[k].num() : 0);
@@ -846,6 +865,7 @@ class Classifier : public jb::mix::Mixable {
     std::lock_guard<std::mutex> g(mu_);
     HIPCHK(hipDeviceSynchronize());
     labels_.clear();
+    labels_kept_ = 0;
     alloc_locked(LC, true);
     size_t o = 4;
     std::vector<std::pair<std::string, bool>> dead;
@@ -953,16 +973,43 @@ class Classifier : public jb::mix::Mixable {
     HIPCHK(hipMemsetD32Async((hipDeviceptr_t)d, (int)one, n, compute_));
   }
 
+  // bytes of W, S and the active mask at label capacity LC
+  size_t table_bytes(int LC) const {
+    return (size_t)H_ * LC * 4 * (use_s_ ? 2 : 1) + (size_t)LC * 4;
+  }
+  static size_t device_free_bytes() {
+    size_t fr = 0, total = 0;
+    if (hipMemGetInfo(&fr, &total) != hipSuccess) {
+      (void)hipGetLastError();
+      return 0;
+    }
+    return fr;
+  }
+  GrowthRefused no_room(int n, int LC, size_t free_now) const {
+    return GrowthRefused("no room for " + std::to_string(n) + " labels: label capacity " +
+                              std::to_string(LC) + " at hash_max_size " + std::to_string(H_) +
+                              " needs " + std::to_string(table_bytes(LC)) + " bytes for its tables, " +
+                              std::to_string(free_now) + " bytes are free (lower hash_max_size)");
+  }
+  // growing allocates the new tables while the old ones are alive: refuse
+  // before anything changes when they do not fit
+  void check_room_locked(int n, int LC) {
+    const size_t fr = device_free_bytes();
+    if (table_bytes(LC) > fr) throw no_room(n, LC, fr);
+  }
+
   // (re)allocate the tables for LC label columns (copy: keep old columns)
   void alloc_locked(int LC, bool fresh) {
     float* W = nullptr;
     float* S = nullptr;
-    HIPCHK(hipMalloc((void**)&W, (size_t)H_ * LC * 4));
-    HIPCHK(hipMemsetAsync(W, 0, (size_t)H_ * LC * 4, compute_));
-    if (use_s_) {
-      HIPCHK(hipMalloc((void**)&S, (size_t)H_ * LC * 4));
-      fill_ones(S, (size_t)H_ * LC);
+    if (hipMalloc((void**)&W, (size_t)H_ * LC * 4) != hipSuccess ||
+        (use_s_ && hipMalloc((void**)&S, (size_t)H_ * LC * 4) != hipSuccess)) {
+      (void)hipGetLastError();       // the old tables stay as they are
+      if (W) (void)hipFree(W);
+      throw no_room(labels_.size(), LC, device_free_bytes());
     }
+    HIPCHK(hipMemsetAsync(W, 0, (size_t)H_ * LC * 4, compute_));
+    if (use_s_) fill_ones(S, (size_t)H_ * LC);
     if (!fresh && LC_ && W_) {
       HIPCHK(hipMemcpy2DAsync(W, (size_t)LC * 4, W_, (size_t)LC_ * 4, (size_t)LC_ * 4, H_,
                               hipMemcpyDeviceToDevice, compute_));
@@ -990,11 +1037,14 @@ class Classifier : public jb::mix::Mixable {
     if (v == label_version_) return;
     const int n = labels_.size();
     if (n > LC_) {
-      int cap = -1;
-      for (int c : kLabelCaps)
-        if (c >= n) { cap = c; break; }
-      if (cap < 0) throw std::runtime_error("at most 1024 labels are supported");
-      alloc_locked(cap, false);
+      try {
+        const int cap = label_cap_for((size_t)n);
+        if (cap > kTemplateMaxLC) check_room_locked(n, cap);
+        alloc_locked(cap, false);
+      } catch (const GrowthRefused&) {
+        labels_.truncate(labels_kept_);   // the labels that asked for it go again
+        throw;
+      }
     }
     auto names = labels_.names();
     auto alive = labels_.alive();
@@ -1029,6 +1079,7 @@ class Classifier : public jb::mix::Mixable {
     lt_cap_ = cap;
     lt_blob_len_ = (int64_t)blob.size();
     label_version_ = v;
+    labels_kept_ = n;
   }
 
   // models/classifier.py _hot_wanted
@@ -1288,6 +1339,7 @@ class Classifier : public jb::mix::Mixable {
   bool use_s_ = false;
   uint64_t H_ = 0;
   int LC_ = 0;
+  int labels_kept_ = 0;     // label count at the last successful sync_labels_locked
   float* W_ = nullptr;
   float* S_ = nullptr;
   int32_t* active_ = nullptr;
@@ -1416,6 +1468,7 @@ class HostClassifier : public jb::mix::Mixable {
     H_ = cfg.rules.H;
     conv_.configure(cfg.rules, cfg.wide, cfg.wrules);
     labels_.clear();
+    labels_kept_ = 0;
     count_base_.clear();
     alloc_locked(kLabelCaps[0], true);
     if (mixing_) touched_.assign(H_, 1);
@@ -1525,6 +1578,7 @@ class HostClassifier : public jb::mix::Mixable {
     std::lock_guard<std::mutex> g(mu_);
     count_base_.clear();
     labels_.clear();
+    labels_kept_ = 0;
     conv_.clear();
     alloc_locked(kLabelCaps[0], true);
     if (mixing_) touched_.assign(H_, 1);
@@ -1589,11 +1643,8 @@ class HostClassifier : public jb::mix::Mixable {
     if (wv->s.size() != nr * L * 4) throw std::runtime_error("broken model data: W rows");
     std::lock_guard<std::mutex> g(mu_);
     labels_.clear();
-    int cap = -1;
-    for (int c : kLabelCaps)
-      if ((size_t)c >= std::max<size_t>(1, L)) { cap = c; break; }
-    if (cap < 0) throw std::runtime_error("at most 1024 labels are supported");
-    alloc_locked(cap, true);
+    labels_kept_ = 0;
+    alloc_locked(label_cap_for(std::max<size_t>(1, L)), true);
     for (size_t k = 0; k < L; ++k) {
       labels_.get_or_add(lv->a[k].s.data(), lv->a[k].s.size());
       labels_.set_count((int)k, k < cv->a.size() ? (uint64_t)cv->a[k].num() : 0);
@@ -1887,6 +1938,7 @@ class HostClassifier : public jb::mix::Mixable {
     if (!apply || grp.rank() == src) return;
     std::lock_guard<std::mutex> g(mu_);
     labels_.clear();
+    labels_kept_ = 0;
     alloc_locked(LC, true);
     size_t o = 4;
     count_base_.clear();
@@ -1997,16 +2049,18 @@ class HostClassifier : public jb::mix::Mixable {
     if (v == label_version_) return;
     const int n = labels_.size();
     if (n > LC_) {
-      int cap = -1;
-      for (int c : kLabelCaps)
-        if (c >= n) { cap = c; break; }
-      if (cap < 0) throw std::runtime_error("at most 1024 labels are supported");
-      alloc_locked(cap, false);
+      try {
+        alloc_locked(label_cap_for((size_t)n), false);
+      } catch (const GrowthRefused&) {
+        labels_.truncate(labels_kept_);   // the labels that asked for it go again
+        throw;
+      }
     }
     auto alive = labels_.alive();
     active_.assign((size_t)LC_, 0);
     for (size_t i = 0; i < alive.size() && i < (size_t)LC_; ++i) active_[i] = alive[i] ? 1 : 0;
     label_version_ = v;
+    labels_kept_ = n;
   }
 
   // [W columns | S columns] of the union rows, in canonical label order
@@ -2060,6 +2114,7 @@ class HostClassifier : public jb::mix::Mixable {
   std::mutex mu_;
   Config cfg_;
   int mid_ = 0, LC_ = 0;
+  int labels_kept_ = 0;     // label count at the last successful sync_labels_locked
   float C_ = 1.f;
   bool use_s_ = false;
   uint64_t H_ = 0;

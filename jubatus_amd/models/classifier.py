@@ -31,9 +31,9 @@ from .._native import native
 from ..fv_converter.converter import DatumToFvConverter
 from ..fv_converter.datum import as_datum
 from . import linear_oracle as lo
+from .label_caps import LABEL_CAPS, TEMPLATE_MAX_LC
 
 LINEAR_METHODS = ("perceptron", "PA", "PA1", "PA2", "CW", "AROW", "NHERD")
-LABEL_CAPS = (8, 16, 32, 64, 128, 256, 512, 1024)
 
 
 class ClassifierConfigError(ValueError):
@@ -51,6 +51,16 @@ def dist_all_reduce(t, op: str, group):
         return None
     o = dist.ReduceOp.MAX if op == "max" else dist.ReduceOp.SUM
     return dist.all_reduce(t, op=o, group=group, async_op=True)
+
+
+def device_free_bytes(device: Any) -> int | None:
+    """Free memory where the tables of ``device`` live, in bytes; None for
+    host tables, which are not checked. The one place the growth check reads
+    it, so a test can put another function here."""
+    if device is None:
+        return None
+    import torch
+    return int(torch.cuda.mem_get_info(device)[0])
 
 
 def _label_cap(n: int) -> int:
@@ -140,6 +150,7 @@ class LinearClassifier:
         self._touched_valid = True
         self._last_mix: dict = {}
         self._mix_job = None      # TableMix of an overlapped MIX in flight
+        self._labels_kept = 0     # label count at the last successful _sync_labels
         self._alloc(LABEL_CAPS[0])
 
     # ------------------------------------------------------------ storage
@@ -170,8 +181,8 @@ class LinearClassifier:
                 W[:, :self.LC].copy_(self.W)
                 if P is not None:
                     P[:, :self.LC].copy_(self.P)
-            self.W, self.P = W, P
-            self.active = t.zeros(LC, dtype=t.int32, device=self.device)
+            active = t.zeros(LC, dtype=t.int32, device=self.device)
+            self.W, self.P, self.active = W, P, active
         else:
             W = np.zeros((H, LC), dtype=np.float32)
             P = np.ones((H, LC), dtype=np.float32) if self.use_s else None
@@ -184,6 +195,37 @@ class LinearClassifier:
         self.LC = LC
         self._label_version = -1
 
+    def table_bytes(self, LC: int) -> int:
+        """bytes of W, P and the active mask at label capacity ``LC``"""
+        wb = 2 if self.weight_dtype == "bf16" else 4
+        return self.H * LC * (wb + (4 if self.use_s else 0)) + 4 * LC
+
+    def _grow(self, n: int) -> None:
+        """tables for ``n`` labels. The new tables are allocated while the old
+        ones are alive, so a capacity above TEMPLATE_MAX_LC is first compared
+        with the free memory; a refusal (or a failed allocation) leaves W, P
+        and LC as they were."""
+        LC = _label_cap(n)
+        if LC <= TEMPLATE_MAX_LC:
+            self._alloc(LC)
+            return
+        need = self.table_bytes(LC)
+        free = device_free_bytes(self.device)
+
+        def refuse(free_now):
+            return ClassifierConfigError(
+                f"no room for {n} labels: label capacity {LC} at hash_max_size {self.H} needs "
+                f"{need} bytes for its tables, {free_now} bytes are free "
+                "(lower hash_max_size or use weight_dtype bf16)")
+        if free is not None and need > free:
+            raise refuse(free)
+        try:
+            self._alloc(LC)
+        except (MemoryError, RuntimeError) as e:
+            if not (isinstance(e, MemoryError) or "out of memory" in str(e).lower()):
+                raise
+            raise refuse(device_free_bytes(self.device)) from e
+
     def _wdt(self):
         return self.torch.bfloat16 if self.weight_dtype == "bf16" else self.torch.float32
 
@@ -194,7 +236,12 @@ class LinearClassifier:
             return
         n = self.labels.size()
         if n > self.LC:
-            self._alloc(_label_cap(n))
+            try:
+                self._grow(n)
+            except ClassifierConfigError:
+                # refused: the labels registered since the last sync go again
+                self.labels.truncate(self._labels_kept)
+                raise
         alive = self.labels.alive()
         mask = np.zeros(self.LC, dtype=np.int32)
         mask[:len(alive)] = np.asarray(alive, dtype=np.int32)
@@ -203,6 +250,7 @@ class LinearClassifier:
         else:
             self.active[:] = mask
         self._label_version = v
+        self._labels_kept = n
 
     # -------------------------------------------------------------- train
     def _mode(self, nstreams: int) -> int:
@@ -615,6 +663,7 @@ class LinearClassifier:
         with self._lock:
             self._drain()
             self.labels.clear()
+            self._labels_kept = 0
             self.LC = 0
             self._alloc(LABEL_CAPS[0])
             self.conv.weights.clear()
@@ -673,6 +722,7 @@ class LinearClassifier:
                 raise ValueError("model hash_max_size differs from the configuration")
             labels = [(x.decode() if isinstance(x, bytes) else x) for x in obj["labels"]]
             self.labels.clear()
+            self._labels_kept = 0
             self.LC = 0
             self._alloc(_label_cap(max(1, len(labels))))
             for i, (name, cnt) in enumerate(zip(labels, obj["counts"])):
@@ -730,6 +780,7 @@ class LinearClassifier:
                     if P is not None:
                         P[:, c] = self.P[:, old[n]]
         self.labels.clear()
+        self._labels_kept = 0
         for c, n in enumerate(order):
             self.labels.get_or_add(n)
             self.labels.set_count(c, counts.get(n, 0))
@@ -914,6 +965,7 @@ class LinearClassifier:
             me = dist.get_rank()
             if me != src and apply:
                 self.labels.clear()
+                self._labels_kept = 0
                 self.LC = 0
                 self._alloc(_label_cap(max(1, len(names))))
                 for i, (n, c) in enumerate(zip(names, counts)):

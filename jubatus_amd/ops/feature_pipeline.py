@@ -581,6 +581,8 @@ class FeaturePipeline:
         if not self.fast:
             return None
         LC = W.shape[1]
+        if LC > hip.DIRECT_MAX_LC:
+            return None
         d = self._direct
         if d is None or d["LC"] < LC:
             cap, slots = hip.DIRECT_MAX_SAMPLES, hip.DIRECT_MAX_SLOTS

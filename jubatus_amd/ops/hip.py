@@ -15,6 +15,7 @@ import time
 import torch
 
 from .._native import hip_lib
+from ..models.label_caps import CHUNK_LABELS, LABEL_CAPS, TEMPLATE_MAX_LC
 from ..utils import trace
 
 _c_void_p = ctypes.c_void_p
@@ -46,6 +47,11 @@ _SIGS = {
     "jb_linear_train_bf16": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
                                     _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _f32, _i32,
                                     _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p]),
+    "jb_linear_train_chunked": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
+                                       _c_void_p, _i32, _c_void_p, _c_void_p, _i32, _i32, _f32,
+                                       _i32, _i32, _c_void_p, _c_void_p, _c_void_p]),
+    "jb_linear_classify_chunked": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32,
+                                          _i32, _c_void_p, _c_void_p]),
     "jb_linear_classify_bf16": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32,
                                        _c_void_p, _c_void_p]),
     "jb_classify_direct_bf16": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _i32,
@@ -598,7 +604,6 @@ def lof_score(ts, td, st, store: int, out: "HostBuffer", max_missing: int) -> No
 
 _fns: dict = {}
 
-LABEL_CAPS = (8, 16, 32, 64, 128, 256, 512, 1024)
 # storage types of the linear W table (P / S stays fp32)
 W_DTYPES = (torch.float32, torch.bfloat16)
 # EXACT: one stream; SERIAL: several streams with the result of applying them
@@ -848,11 +853,15 @@ class SerialScratch:
         self.device = device
         self.buf = None
         self.nbytes = 0
+        self.lc = 0              # label capacity of the last batch (0: not given)
 
     def last_batch(self) -> dict:
         """diagnostics of the last kSerial batch (synchronises): first sample
         left to the sequential kernel, batch end, exact steps, rounds"""
-        if self.buf is None:
+        # a batch at a label capacity above TEMPLATE_MAX_LC runs no committer:
+        # its scratch holds the stream span only, no tail words
+        if self.buf is None or self.lc > TEMPLATE_MAX_LC or \
+                self.buf.numel() < 8 * TAIL_WORDS["kTailWords"]:
             return {}
         v = self.buf[:8 * TAIL_WORDS["kTailWords"]].view(torch.int64).tolist()
 
@@ -904,6 +913,7 @@ class SerialScratch:
 
     def ptr(self, n_max: int, lc: int = 0) -> int:
         """lc: the model's label capacity (0: the largest need, any capacity)"""
+        self.lc = int(lc)
         need = int(_fn("jb_serial_scratch_bytes_lc")(int(n_max), int(lc)) if lc > 0
                    else _fn("jb_serial_scratch_bytes")(int(n_max)))
         if need > self.nbytes:
@@ -957,6 +967,68 @@ def hot_detect(row_ptr: torch.Tensor, n: int, fidx: torch.Tensor, max_slots: int
                               int(min_count), int(max_rows), _p(hot.gkey), _p(hot.gcnt),
                               hot.CAP, _p(hot.rows), _p(hot.n), _stream())
     _check(rc, "jb_hot_detect")
+
+
+def _chunked_lc(LC: int) -> None:
+    if LC % CHUNK_LABELS or not CHUNK_LABELS <= LC <= LABEL_CAPS[-1]:
+        raise ValueError(f"label capacity {LC}: the chunked kernels take multiples of "
+                         f"{CHUNK_LABELS} up to {LABEL_CAPS[-1]}")
+
+
+def linear_train_chunked(row_ptr: torch.Tensor, fidx: torch.Tensor, fval: torch.Tensor,
+                         labels: torch.Tensor, stream_ptr: torch.Tensor, nstreams: int,
+                         W: torch.Tensor, S: torch.Tensor | None, active: torch.Tensor,
+                         method: int, C: float, mode: int, waves: int = 0,
+                         stats: torch.Tensor | None = None,
+                         touched: torch.Tensor | None = None) -> None:
+    """The run-time label capacity train kernel (csrc/hip/linear_chunked.hip),
+    which ``linear_train`` reaches for capacities above TEMPLATE_MAX_LC. mode:
+    UPDATE_EXACT (one stream), UPDATE_ATOMIC or UPDATE_HOGWILD. waves: 1, 4 or
+    16 wave64s per stream, 0 for the library's default (JUBATUS_LABEL_WAVES)."""
+    LC = W.shape[1]
+    _chunked_lc(LC)
+    if waves not in (0, 1, 4, 16):
+        raise ValueError("waves: 0 (default), 1, 4 or 16")
+    if mode not in (UPDATE_EXACT, UPDATE_ATOMIC, UPDATE_HOGWILD) or \
+            (mode == UPDATE_EXACT and nstreams > 1):
+        raise ValueError("linear_train_chunked: exact (one stream), atomic or hogwild")
+    _dev(W, W.dtype if W.dtype in W_DTYPES else torch.float32, "W")
+    _dev(active, torch.int32, "active")
+    if active.numel() < LC:
+        raise ValueError("active mask shorter than label capacity")
+    if method >= METHODS["CW"]:
+        if S is None or S.shape != W.shape:
+            raise ValueError("CW/AROW/NHERD need a covariance table shaped like W")
+        _dev(S, torch.float32, "S")
+    if stream_ptr.numel() < nstreams + 1:
+        raise ValueError("stream_ptr shorter than nstreams+1")
+    if stats is not None:
+        _dev(stats, torch.int64, "stats")
+        if stats.numel() < 2:
+            raise ValueError("stats needs 2 counters")
+    if touched is not None:
+        _dev(touched, torch.uint8, "touched")
+        if touched.numel() < W.shape[0]:
+            raise ValueError("touched shorter than the table")
+    rc = _fn("jb_linear_train_chunked")(
+        _p(row_ptr), _p(fidx), _p(fval), _p(labels), _p(stream_ptr), nstreams, _p(W),
+        1 if W.dtype == torch.bfloat16 else 0, _p(S) if S is not None else None, _p(active), LC,
+        method, float(C), int(mode), int(waves), _p(stats), _p(touched), _stream())
+    _check(rc, "jb_linear_train_chunked")
+
+
+def linear_classify_chunked(row_ptr: torch.Tensor, fidx: torch.Tensor, fval: torch.Tensor, n: int,
+                            W: torch.Tensor, out: torch.Tensor) -> None:
+    LC = W.shape[1]
+    _chunked_lc(LC)
+    _dev(W, W.dtype if W.dtype in W_DTYPES else torch.float32, "W")
+    _dev(out, torch.float32, "out")
+    if out.numel() < n * LC or row_ptr.numel() < n + 1:
+        raise ValueError("linear_classify_chunked: output / row_ptr too small")
+    rc = _fn("jb_linear_classify_chunked")(_p(row_ptr), _p(fidx), _p(fval), n, _p(W),
+                                           1 if W.dtype == torch.bfloat16 else 0, LC, _p(out),
+                                           _stream())
+    _check(rc, "jb_linear_classify_chunked")
 
 
 def linear_classify(row_ptr: torch.Tensor, fidx: torch.Tensor, fval: torch.Tensor, n: int,
@@ -1121,6 +1193,7 @@ _tb_checked = False
 # ------------------------------------------------------------ direct classify
 DIRECT_MAX_SAMPLES = 32     # csrc/hip/classify_direct.hip kDirectMaxSamples
 DIRECT_MAX_SLOTS = 320      # kDirectMaxSlots
+DIRECT_MAX_LC = TEMPLATE_MAX_LC   # larger label capacities use the batch path
 
 
 class HostBuffer:
@@ -1158,6 +1231,8 @@ def classify_direct(idx_ptr: int, val_ptr: int, row_ptr_ptr: int, n: int, W: tor
     LC = W.shape[1]
     if LC not in LABEL_CAPS:
         raise ValueError(f"label capacity {LC} not supported")
+    if LC > DIRECT_MAX_LC:
+        return False
     _dev(W, W.dtype if W.dtype in W_DTYPES else torch.float32, "W")
     if out.nbytes < n * LC * 4 or done.nbytes < 4 * n:
         raise ValueError("classify_direct: output buffer too small")

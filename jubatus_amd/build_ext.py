@@ -139,6 +139,8 @@ TOOLS = {
     # host-only rehearsal of the native distributed model plane (jb_mix_group.hpp)
     "jb_mix_rehearsal": (["tools/jb_mix_rehearsal.cpp", "native/jb_rpc.cpp"],
                          ["native", "server", "../client_cpp/include"]),
+    # the native wide converter over packed rule tables, for instrumented builds
+    "jb_hostfv_wide_check": (["tools/jb_hostfv_wide_check.cpp"], ["native"]),
 }
 
 

@@ -7,6 +7,21 @@
 // converter (fv_converter/converter.py `_convert`); slots a rule leaves
 // unused are idx -1, as on the fixed-slot fast path (fv_hash.hip).
 //
+// Num filters with a built-in method are derived rows of the num rule table,
+// the layout of the fixed-slot path (jb_fv.hpp, ../native/jb_fv_layout.hpp):
+// nbase base rows, then nbase rows per filter chain, chain-major. Only the
+// feature order differs from that path, because the combination pairs a < b
+// depend on it: converter.py `_filtered` appends the derived values filter by
+// filter, so a datum's num features come in blocks - block 0 the base rows on
+// the original values, block c the rows of chain c - 1 (the chains in
+// gpu_path._filter_chains order) - and inside a block in datum order, rule
+// innermost. fvw_emit_kernel walks the datum's num_values once per block from
+// a saved reader. A derived row's value is its chain in fp64 (filter_apply, no
+// contraction), then num / log as on an original value, then one cast to fp32.
+// Its name is key + suffix like a base row's (the suffix holds the chain's
+// suffixes and "@type"), which is what the combination matchers see:
+// "height_z@num". Derived hits count toward B_i and kWideMaxBase.
+//
 // Layout per datum i (row_ptr from fvw_count_kernel + a scan): a base
 // region of B_i slots (upper bound: every token, every matching num rule)
 // followed by ncomb x B_i (B_i - 1) / 2 combination slots (pair (a, b),
@@ -97,7 +112,11 @@ __device__ __forceinline__ bool wide_count_datum(Reader& rd, const GpuRule* __re
     int kn;
     double x;
     if (!rd.raw(&k, &kn) || !rd.number(&x)) return false;
-    for (int r = 0; r < nn; ++r) b += key_matches(nr[r], blob, k, kn);
+    for (int r = 0; r < nn; ++r) {      // base and derived rows alike: the order is emit's
+      double y = x;
+      b += (nr[r].value_kind & kDerivedRow) ? chain_matches(nr[r], blob, k, kn, &y)
+                                            : key_matches(nr[r], blob, k, kn);
+    }
   }
   *base = b;
   return rd.ok;
@@ -125,7 +144,7 @@ __global__ __launch_bounds__(256) void fvw_count_kernel(
 __global__ __launch_bounds__(256) void fvw_emit_kernel(
     const uint8_t* __restrict__ buf, int64_t buf_len, const int64_t* __restrict__ datum_off,
     const int32_t* __restrict__ datum_len, int n, const int64_t* __restrict__ row_ptr,
-    const GpuRule* __restrict__ sr, int ns, const GpuRule* __restrict__ nr, int nn,
+    const GpuRule* __restrict__ sr, int ns, const GpuRule* __restrict__ nr, int nn, int nbase,
     const uint8_t* __restrict__ blob, uint64_t H, int32_t* __restrict__ out_idx,
     float* __restrict__ out_val, uint64_t* __restrict__ out_h, SlotName* __restrict__ out_name,
     uint8_t* __restrict__ out_gw, int32_t* __restrict__ err) {
@@ -135,16 +154,19 @@ __global__ __launch_bounds__(256) void fvw_emit_kernel(
   const int64_t end = off + datum_len[i] < buf_len ? off + datum_len[i] : buf_len;
   Reader rd{buf + off, buf + end, true};
   int64_t slot = row_ptr[i];
+  // a datum the count pass refused (malformed, or above kWideMaxBase) owns no
+  // slots: nothing is written past slot_end
+  const int64_t slot_end = row_ptr[i + 1];
   bool good = rd.array_len() >= 2;
   const int64_t nsv = good ? rd.array_len() : -1;
-  for (int64_t a = 0; a < nsv && rd.ok; ++a) {
+  for (int64_t a = 0; a < nsv && rd.ok && good; ++a) {
     if (rd.array_len() != 2) { good = false; break; }
     const uint8_t *k, *v;
     int kn, vn;
     if (!rd.raw(&k, &kn) || !rd.raw(&v, &vn)) { good = false; break; }
     uint64_t hk = fnv_bytes(kFnvOffset, k, kn);
     hk = fnv_byte(hk, '$');
-    for (int r = 0; r < ns; ++r) {
+    for (int r = 0; r < ns && good; ++r) {
       const GpuRule rule = sr[r];
       if (!key_matches(rule, blob, k, kn)) continue;
       const int kind = rule.value_kind & 15, sw = rule.value_kind >> 4 & 15;
@@ -152,6 +174,7 @@ __global__ __launch_bounds__(256) void fvw_emit_kernel(
       const int m = wide_tokens(kind, rule.pad, v, vn);
       const int64_t g0 = slot;
       for (int t = 0; t < m; ++t) {
+        if (slot >= slot_end) { good = false; break; }
         int to, tl;
         wide_token(kind, rule.pad, v, vn, t, &to, &tl);
         const uint64_t h = fnv_bytes(fnv_bytes(hk, v + to, tl), blob + rule.suffix_off,
@@ -182,24 +205,36 @@ __global__ __launch_bounds__(256) void fvw_emit_kernel(
       }
     }
   }
-  const int64_t nnv = (good && rd.ok) ? rd.array_len() : -1;
-  for (int64_t a = 0; a < nnv && rd.ok; ++a) {
-    if (rd.array_len() != 2) { good = false; break; }
-    const uint8_t* k;
-    int kn;
-    double x;
-    if (!rd.raw(&k, &kn) || !rd.number(&x)) { good = false; break; }
-    const uint64_t hk = fnv_bytes(kFnvOffset, k, kn);
-    for (int r = 0; r < nn; ++r) {
-      const GpuRule rule = nr[r];
-      if (!key_matches(rule, blob, k, kn)) continue;
-      const uint64_t h = fnv_bytes(hk, blob + rule.suffix_off, rule.suffix_len);
-      out_idx[slot] = (int32_t)hash_to_index(h, H);
-      out_val[slot] = (float)(rule.value_kind == 1 ? log(x > 1.0 ? x : 1.0) : x);
-      out_h[slot] = h;
-      out_gw[slot] = 0;
-      out_name[slot] = SlotName{(int32_t)(k - buf), kn, -1, 0, 1000 + r};
-      ++slot;
+  // num features block by block: the base rows on the original values, then
+  // the rows of each filter chain, every block over num_values from the start
+  const Reader nums = rd;
+  const int nblk = (good && rd.ok) ? (nbase > 0 ? nn / nbase : 1) : 0;
+  for (int blk = 0; blk < nblk && good && rd.ok; ++blk) {
+    rd = nums;
+    const GpuRule* __restrict__ rows = nr + blk * nbase;
+    const int64_t nnv = rd.array_len();
+    for (int64_t a = 0; a < nnv && rd.ok && good; ++a) {
+      if (rd.array_len() != 2) { good = false; break; }
+      const uint8_t* k;
+      int kn;
+      double x;
+      if (!rd.raw(&k, &kn) || !rd.number(&x)) { good = false; break; }
+      const uint64_t hk = fnv_bytes(kFnvOffset, k, kn);
+      for (int r = 0; r < nbase; ++r) {
+        const GpuRule rule = rows[r];
+        double y = x;
+        const bool hit = (rule.value_kind & kDerivedRow) ? chain_matches(rule, blob, k, kn, &y)
+                                                         : key_matches(rule, blob, k, kn);
+        if (!hit) continue;
+        if (slot >= slot_end) { good = false; break; }
+        const uint64_t h = fnv_bytes(hk, blob + rule.suffix_off, rule.suffix_len);
+        out_idx[slot] = (int32_t)hash_to_index(h, H);
+        out_val[slot] = (float)((rule.value_kind & 1) ? log(y > 1.0 ? y : 1.0) : y);
+        out_h[slot] = h;
+        out_gw[slot] = 0;
+        out_name[slot] = SlotName{(int32_t)(k - buf), kn, -1, 0, 1000 + blk * nbase + r};
+        ++slot;
+      }
     }
   }
   if (!good || !rd.ok) atomicOr(err, 2);
@@ -287,13 +322,15 @@ extern "C" int jb_fvw_count(const uint8_t* buf, int64_t buf_len, const int64_t* 
 
 extern "C" int jb_fvw_emit(const uint8_t* buf, int64_t buf_len, const int64_t* datum_off,
                            const int32_t* datum_len, int n, const int64_t* row_ptr, const void* sr,
-                           int ns, const void* nr, int nn, const uint8_t* blob, uint64_t H,
-                           int32_t* out_idx, float* out_val, uint64_t* out_h, void* out_name,
-                           uint8_t* out_gw, int32_t* err, hipStream_t stream) {
+                           int ns, const void* nr, int nn, int nbase, const uint8_t* blob,
+                           uint64_t H, int32_t* out_idx, float* out_val, uint64_t* out_h,
+                           void* out_name, uint8_t* out_gw, int32_t* err, hipStream_t stream) {
   if (n <= 0) return 0;
+  // nn = nbase x (1 + filter chains): base rows, then the chains' rows
+  if (nbase < 0 || nbase > nn || (nbase ? nn % nbase != 0 : nn != 0)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(jb::fvw_emit_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, buf,
                      buf_len, datum_off, datum_len, n, row_ptr, (const jb::GpuRule*)sr, ns,
-                     (const jb::GpuRule*)nr, nn, blob, H, out_idx, out_val, out_h,
+                     (const jb::GpuRule*)nr, nn, nbase, blob, H, out_idx, out_val, out_h,
                      (jb::SlotName*)out_name, out_gw, err);
   return (int)hipGetLastError();
 }

@@ -59,9 +59,9 @@ int jb_fvw_count(const uint8_t* buf, int64_t buf_len, const int64_t* datum_off,
                  int32_t* err, hipStream_t stream);
 int jb_fvw_emit(const uint8_t* buf, int64_t buf_len, const int64_t* datum_off,
                 const int32_t* datum_len, int n, const int64_t* row_ptr, const void* sr, int ns,
-                const void* nr, int nn, const uint8_t* blob, uint64_t H, int32_t* out_idx,
-                float* out_val, uint64_t* out_h, void* out_name, uint8_t* out_gw, int32_t* err,
-                hipStream_t stream);
+                const void* nr, int nn, int nbase, const uint8_t* blob, uint64_t H,
+                int32_t* out_idx, float* out_val, uint64_t* out_h, void* out_name, uint8_t* out_gw,
+                int32_t* err, hipStream_t stream);
 int jb_fvw_comb(const uint8_t* buf, int n, const int64_t* row_ptr, const int64_t* base_cnt,
                 const void* sr, const void* nr, const void* cr, int ncomb, const uint8_t* blob,
                 uint64_t H, int32_t* idx, float* val, const uint64_t* hs, const void* names,

@@ -52,6 +52,45 @@ inline double filter_apply(int method, double a, double b, bool truncate, double
   }
 }
 
+// the matcher over key || ext (jb_fv.hpp ext_key_matches)
+inline bool host_ext_key_matches(int kind, const uint8_t* m, uint32_t mn, const uint8_t* k,
+                                 uint32_t kn, const uint8_t* e, uint32_t en) {
+  if (kind == 0) return true;
+  const uint32_t tn = kn + en;
+  if (kind == 3 && tn != mn) return false;
+  if (tn < mn) return false;
+  const uint32_t start = kind == 2 ? tn - mn : 0;
+  for (uint32_t i = 0; i < mn; ++i) {
+    const uint32_t p = start + i;
+    if ((p < kn ? k[p] : e[p - kn]) != m[i]) return false;
+  }
+  return true;
+}
+
+// a derived row on one value (jb_fv.hpp chain_matches), shared by the
+// fixed-slot hasher below and the wide converter (jb_hostfv_wide.hpp); the
+// programme is read byte-wise, std::vector gives the blob no alignment
+inline bool host_chain_matches(const HostRule& r, const uint8_t* blob, const uint8_t* k,
+                               uint32_t kn, double* y) {
+  const uint8_t* pg = blob + r.pad;
+  int32_t n_steps, ext_len;
+  memcpy(&n_steps, pg, 4);
+  memcpy(&ext_len, pg + 4, 4);
+  const uint8_t* ext = blob + r.suffix_off;
+  double v = *y;
+  for (int32_t j = 0; j < n_steps; ++j) {
+    FilterStep s;
+    memcpy(&s, pg + 8 + sizeof(FilterStep) * (size_t)j, sizeof s);
+    if (!host_ext_key_matches(s.match_kind, blob + s.match_off, (uint32_t)s.match_len, k, kn,
+                              ext, (uint32_t)s.ext_len))
+      return false;
+    v = filter_apply(s.method, s.a, s.b, s.truncate != 0, v);
+  }
+  *y = v;
+  return host_ext_key_matches(r.match_kind, blob + r.match_off, (uint32_t)r.match_len, k, kn,
+                              ext, (uint32_t)ext_len);
+}
+
 class HostFvHasher {
  public:
   HostFvHasher(const uint8_t* srules, int n_srules, const uint8_t* nrules, int n_nrules,
@@ -94,43 +133,6 @@ class HostFvHasher {
     return memcmp(base, m, mn) == 0;
   }
 
-  // the matcher over key || ext (jb_fv.hpp ext_key_matches)
-  static bool match_ext(int kind, const uint8_t* m, uint32_t mn, const uint8_t* k, uint32_t kn,
-                        const uint8_t* e, uint32_t en) {
-    if (kind == 0) return true;
-    const uint32_t tn = kn + en;
-    if (kind == 3 && tn != mn) return false;
-    if (tn < mn) return false;
-    const uint32_t start = kind == 2 ? tn - mn : 0;
-    for (uint32_t i = 0; i < mn; ++i) {
-      const uint32_t p = start + i;
-      if ((p < kn ? k[p] : e[p - kn]) != m[i]) return false;
-    }
-    return true;
-  }
-
-  // a derived row on one value (jb_fv.hpp chain_matches); the programme is
-  // read byte-wise, std::vector gives it no alignment
-  bool chain(const HostRule& r, const uint8_t* k, uint32_t kn, double* y) const {
-    const uint8_t* pg = blob_.data() + r.pad;
-    int32_t n_steps, ext_len;
-    memcpy(&n_steps, pg, 4);
-    memcpy(&ext_len, pg + 4, 4);
-    const uint8_t* ext = blob_.data() + r.suffix_off;
-    double v = *y;
-    for (int32_t j = 0; j < n_steps; ++j) {
-      FilterStep s;
-      memcpy(&s, pg + 8 + sizeof(FilterStep) * (size_t)j, sizeof s);
-      if (!match_ext(s.match_kind, blob_.data() + s.match_off, (uint32_t)s.match_len, k, kn, ext,
-                     (uint32_t)s.ext_len))
-        return false;
-      v = filter_apply(s.method, s.a, s.b, s.truncate != 0, v);
-    }
-    *y = v;
-    return match_ext(r.match_kind, blob_.data() + r.match_off, (uint32_t)r.match_len, k, kn, ext,
-                     (uint32_t)ext_len);
-  }
-
   int datum(Cursor& c, int32_t* idx, float* val, int64_t max_slots, int64_t* slots) const {
     uint32_t top, ns, nn;
     if (!c.array(&top) || top < 2) return 1;
@@ -162,7 +164,8 @@ class HostFvHasher {
       for (const HostRule& r : n_) {
         if (*slots >= max_slots) return 2;
         double y = x;
-        if ((r.value_kind & kDerivedRow) ? chain(r, k, kn, &y) : match(r, k, kn)) {
+        if ((r.value_kind & kDerivedRow) ? host_chain_matches(r, blob_.data(), k, kn, &y)
+                                         : match(r, k, kn)) {
           idx[*slots] = (int32_t)hash_to_index(fnv_bytes(hk, blob_.data() + r.suffix_off,
                                                          (size_t)r.suffix_len), H_);
           val[*slots] = (r.value_kind & 1) ? logf(fmaxf(1.f, (float)y)) : (float)y;

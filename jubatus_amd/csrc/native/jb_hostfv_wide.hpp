@@ -9,6 +9,16 @@
 // list. Values are computed in double and stored as float, as the Python path
 // does. Rule tables come from fv_converter/gpu_path.py WideRuleTable; the GPU
 // twin is csrc/hip/fv_wide.hip.
+//
+// Num filters reach this converter in one of two ways. A WideRuleTable carries
+// the built-in ones as derived rows of the num rule table (layout:
+// jb_fv_layout.hpp; nbase base rows, then nbase rows per filter chain): no
+// WideExt is needed, and the num features come out in the Python converter's
+// order - the base rows over the datum's values, then chain by chain the
+// derived rows over the same values, value-major and rule-minor inside each
+// block - which is the order the combination pairs are formed in. The native
+// servers (jb_wide_rules.hpp) pack no derived rows and run every filter, the
+// plug-in ones included, through WideExt::nf on the value list instead.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -116,6 +126,9 @@ class HostFvWide {
     if (n_crules) memcpy(c_.data(), crules, sizeof(HostRule) * 2 * n_crules);
     for (const HostRule& r : s_)
       if ((r.value_kind >> 8 & 15) != kGwBin) global_ = true;
+    // the base rows lead; what follows are the filter chains' derived rows
+    while (nbase_ < n_.size() && !(n_[nbase_].value_kind & kDerivedRow)) ++nbase_;
+    nblocks_ = nbase_ ? n_.size() / nbase_ : 1;
   }
 
   // WeightManager storage: df[H], diff[H] (int64) and counts[4] =
@@ -252,6 +265,51 @@ class HostFvWide {
     feats_.push_back(f);
   }
 
+  // The num features of one block over the datum's (filtered) num values, in
+  // value order, rule innermost: block 0 the base rows, block c the derived
+  // rows of filter chain c - 1 (its value: the chain in fp64, then num / log
+  // as on an original value).
+  void num_block(size_t blk) {
+    for (const NV& e : nv_) {
+      const uint8_t* k = e.k;
+      const uint32_t kn = e.kn;
+      const uint64_t hk = fnv_bytes(kFnvOffset, k, kn);
+      for (size_t ri = blk * nbase_; ri < (blk + 1) * nbase_; ++ri) {
+        const HostRule& r = n_[ri];
+        double x = e.x;
+        if ((r.value_kind & kDerivedRow) ? !host_chain_matches(r, blob_.data(), k, kn, &x)
+                                         : !match_key(r, k, kn))
+          continue;
+        const int vk = r.value_kind & ~kDerivedRow;
+        const uint8_t* suf = blob_.data() + r.suffix_off;
+        if (vk == kNumPlugin) {
+          ext_->plugins[(size_t)r.pad]->num_feature(std::string((const char*)k, kn), x, &pnamed_);
+          for (const auto& nv : pnamed_) {
+            const std::string& nm = keep(nv.first);
+            add_feat(WideName{{u8(nm), nullptr, nullptr, nullptr}, {(uint32_t)nm.size(), 0, 0, 0}, 1}, nv.second,
+                     kGwBin);
+          }
+          continue;
+        }
+        if (vk == kNumStr) {      // <key>$<value>@<type>, weight 1
+          const std::string& vs = keep(num_str(x));
+          add_feat(WideName{{k, (const uint8_t*)"$", u8(vs), suf}, {kn, 1, (uint32_t)vs.size(),
+                                                                    (uint32_t)r.suffix_len}, 4},
+                   1.0, kGwBin);
+          continue;
+        }
+        WideFeat f;
+        f.h = fnv_bytes(hk, suf, (size_t)r.suffix_len);
+        f.idx = (int32_t)hash_to_index(f.h, H_);
+        f.w = vk == kNumLog ? log(x > 1.0 ? x : 1.0)
+              : vk == kNumAdd ? x + ext_->addv[(size_t)r.pad] : x;
+        f.gw = kGwBin;
+        f.name = WideName{{k, suf, nullptr, nullptr}, {kn, (uint32_t)r.suffix_len, 0, 0}, 2};
+        feats_.push_back(f);
+      }
+    }
+  }
+
   int datum(Cursor& c, int32_t* idx, float* val, int64_t max_slots, int64_t* slots, bool update) {
     uint32_t top, ns, nn;
     if (!c.array(&top) || top < 2) return 1;
@@ -364,40 +422,7 @@ class HostFvWide {
       }
     }
     if (global_) weigh(update);
-    for (const NV& e : nv_) {
-      const uint8_t* k = e.k;
-      const uint32_t kn = e.kn;
-      const double x = e.x;
-      const uint64_t hk = fnv_bytes(kFnvOffset, k, kn);
-      for (const HostRule& r : n_) {
-        if (!match_key(r, k, kn)) continue;
-        const uint8_t* suf = blob_.data() + r.suffix_off;
-        if (r.value_kind == kNumPlugin) {
-          ext_->plugins[(size_t)r.pad]->num_feature(std::string((const char*)k, kn), x, &pnamed_);
-          for (const auto& nv : pnamed_) {
-            const std::string& nm = keep(nv.first);
-            add_feat(WideName{{u8(nm), nullptr, nullptr, nullptr}, {(uint32_t)nm.size(), 0, 0, 0}, 1}, nv.second,
-                     kGwBin);
-          }
-          continue;
-        }
-        if (r.value_kind == kNumStr) {      // <key>$<value>@<type>, weight 1
-          const std::string& vs = keep(num_str(x));
-          add_feat(WideName{{k, (const uint8_t*)"$", u8(vs), suf}, {kn, 1, (uint32_t)vs.size(),
-                                                                    (uint32_t)r.suffix_len}, 4},
-                   1.0, kGwBin);
-          continue;
-        }
-        WideFeat f;
-        f.h = fnv_bytes(hk, suf, (size_t)r.suffix_len);
-        f.idx = (int32_t)hash_to_index(f.h, H_);
-        f.w = r.value_kind == kNumLog ? log(x > 1.0 ? x : 1.0)
-              : r.value_kind == kNumAdd ? x + ext_->addv[(size_t)r.pad] : x;
-        f.gw = kGwBin;
-        f.name = WideName{{k, suf, nullptr, nullptr}, {kn, (uint32_t)r.suffix_len, 0, 0}, 2};
-        feats_.push_back(f);
-      }
-    }
+    for (size_t blk = 0; blk < nblocks_; ++blk) num_block(blk);
     // binary values: plug-in features <key>$<token>@<type> (others carry none)
     if (top >= 3 && ext_ && !ext_->br.empty()) {
       uint32_t nb;
@@ -508,6 +533,8 @@ class HostFvWide {
   std::vector<uint8_t> blob_;
   uint64_t H_;
   uint64_t Hdf_ = 0;     // 0: the document statistics use H_
+  size_t nbase_ = 0;     // base rows of n_; nblocks_ = 1 + filter chains
+  size_t nblocks_ = 1;
   bool global_ = false;
   int64_t *df_ = nullptr, *diff_ = nullptr, *counts_ = nullptr;
   std::vector<WideFeat> feats_;

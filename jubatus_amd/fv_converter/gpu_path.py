@@ -24,7 +24,22 @@ into the device rule tables.
 * wide rule set (``wide_eligible``, csrc/hip/fv_wide.hip and the native host
   twin csrc/native/jb_hostfv_wide.hpp): adds the ``space`` / ``ngram``
   splitters, tf / log_tf with idf / bm25 global weights and add / mul
-  combinations; no filters on the device (natively WideExt runs them).
+  combinations. Num filters run there under the same conditions and as the
+  same derived rows (one packing helper, ``_pack_num_rows``); what differs is
+  the feature order, which the combination pairs ``i < j`` depend on. The
+  Python converter appends the derived values filter by filter, so a datum's
+  num features come in blocks: the original values, then one block per chain
+  in ``_filter_chains`` order, each block in datum order with the base rules
+  innermost. With two ``*`` filters ``_0`` / ``_1``, values ``a``, ``b`` and
+  the rule ``*`` that is ``a b a_0 b_0 a_1 b_1 a_0_1 b_0_1`` (``@num``). The
+  kernels and the host twin walk the datum's num values once per block. A
+  combination matcher sees a derived feature by its full name
+  (``height_z@num``). The device converts at most 4096 base features per
+  datum (``kWideMaxBase``) and derived features count: with 16 chains every
+  num value is up to 17 features, so a datum reaches the limit 17 times
+  sooner and then fails as before, ``TypeError("malformed datum (device wide
+  converter)")``. The native servers keep running filters of wide configs
+  through ``WideExt`` on the host.
 
 ``gpu_eligible`` is either; regex matchers, string filters, plug-in
 ("dynamic") filters, filter configs above the chain cap and plug-ins keep the
@@ -108,6 +123,58 @@ def _filter_chains(steps):
     return [c[0] for c in chains[1:]]
 
 
+def _filters_ok(conv: DatumToFvConverter) -> bool:
+    """the num filters (if any) run as derived num rows: built-in methods,
+    non-regex keys, at most MAX_FILTER_CHAINS chains"""
+    if not conv.num_filters:
+        return True
+    steps = _filter_steps(conv)
+    return steps is not None and _filter_chains(steps) is not None
+
+
+def _put(blob: bytearray, b: bytes) -> tuple[int, int]:
+    off = len(blob)
+    blob.extend(b)
+    return off, len(b)
+
+
+def _pack_num_rows(conv: DatumToFvConverter, blob: bytearray, is_log) -> tuple[list, int, int]:
+    """The num rule table of both device paths (GpuRuleTable, WideRuleTable),
+    appended to `blob`: the base rows (matcher and "@type" bytes, as before
+    filters were served), then the filters' matcher bytes, the chain programmes
+    (8-byte aligned) and one derived row per (chain, base row), chain-major,
+    with the chain's suffixes + "@type" as its suffix. `is_log(rule)` tells a
+    `log` row. -> (packed rows, base rows, chains)"""
+    nrows, base = [], []
+    for r in conv.num_rules:
+        mo, ml = _put(blob, r.matcher.arg.encode())
+        tail = f"@{r.type_name}".encode()
+        so, sl = _put(blob, tail)
+        vk = 1 if is_log(r) else 0
+        base.append((_KIND[r.matcher.kind], mo, ml, tail, vk))
+        nrows.append(_RULE.pack(_KIND[r.matcher.kind], mo, ml, so, sl, vk, 0.0, 0))
+    chains = []
+    if conv.num_filters:
+        steps = _filter_steps(conv)
+        chains = _filter_chains(steps)
+        args = [_put(blob, st[1]) for st in steps]
+        progs = []
+        for chain in chains:
+            blob.extend(b"\0" * (-len(blob) % 8))
+            prog, ext = bytearray(), 0
+            for f in chain:
+                kind, _, suffix, method, a, b, trunc = steps[f]
+                prog += _STEP.pack(kind, args[f][0], args[f][1], ext, method, trunc, a, b)
+                ext += len(suffix)
+            progs.append(_put(blob, struct.pack("<ii", len(chain), ext) + bytes(prog))[0])
+        for chain, po in zip(chains, progs):
+            ext = b"".join(steps[f][2] for f in chain)
+            for kind, mo, ml, tail, vk in base:
+                so, sl = _put(blob, ext + tail)
+                nrows.append(_RULE.pack(kind, mo, ml, so, sl, vk | _DERIVED_ROW, 0.0, po))
+    return nrows, len(base), len(chains)
+
+
 def fast_eligible(conv: DatumToFvConverter) -> bool:
     """the fixed-slot fast path (fv_hash.hip / scan.hip): one slot per
     (value, rule row), constant string weights; num filters with a built-in
@@ -122,11 +189,7 @@ def fast_eligible(conv: DatumToFvConverter) -> bool:
     for r in conv.num_rules:
         if r.type_name not in ("num", "log") or r.matcher.kind not in _KIND:
             return False
-    if conv.num_filters:
-        steps = _filter_steps(conv)
-        if steps is None or _filter_chains(steps) is None:
-            return False
-    return True
+    return _filters_ok(conv)
 
 
 class GpuRuleTable:
@@ -140,43 +203,14 @@ class GpuRuleTable:
         if not fast_eligible(conv):
             raise ValueError("converter config is not eligible for the GPU fast path")
         blob = bytearray()
-
-        def put(b: bytes) -> tuple[int, int]:
-            off = len(blob)
-            blob.extend(b)
-            return off, len(b)
-
         srows = []
         for r in conv.string_rules:
-            mo, ml = put(r.matcher.arg.encode())
-            so, sl = put(r.suffix.encode())
+            mo, ml = _put(blob, r.matcher.arg.encode())
+            so, sl = _put(blob, r.suffix.encode())
             w = {"bin": 1.0, "tf": 1.0, "log_tf": math.log(2.0)}[r.sw]
             srows.append(_RULE.pack(_KIND[r.matcher.kind], mo, ml, so, sl, 0, w, 0))
-        nrows, base = [], []
-        for r in conv.num_rules:
-            mo, ml = put(r.matcher.arg.encode())
-            so, sl = put(f"@{r.type_name}".encode())
-            vk = 1 if r.type_name == "log" else 0
-            base.append((_KIND[r.matcher.kind], mo, ml, f"@{r.type_name}".encode(), vk))
-            nrows.append(_RULE.pack(_KIND[r.matcher.kind], mo, ml, so, sl, vk, 0.0, 0))
-        if conv.num_filters:
-            steps = _filter_steps(conv)
-            chains = _filter_chains(steps)
-            args = [put(st[1]) for st in steps]
-            progs = []
-            for chain in chains:
-                blob.extend(b"\0" * (-len(blob) % 8))
-                prog, ext = bytearray(), 0
-                for f in chain:
-                    kind, _, suffix, method, a, b, trunc = steps[f]
-                    prog += _STEP.pack(kind, args[f][0], args[f][1], ext, method, trunc, a, b)
-                    ext += len(suffix)
-                progs.append(put(struct.pack("<ii", len(chain), ext) + bytes(prog))[0])
-            for chain, po in zip(chains, progs):
-                ext = b"".join(steps[f][2] for f in chain)
-                for kind, mo, ml, tail, vk in base:
-                    so, sl = put(ext + tail)
-                    nrows.append(_RULE.pack(kind, mo, ml, so, sl, vk | _DERIVED_ROW, 0.0, po))
+        nrows, self.n_base, self.n_chains = _pack_num_rows(
+            conv, blob, lambda r: r.type_name == "log")
         self.n_srules = len(srows)
         self.n_nrules = len(nrows)
         self.srules = np.frombuffer(b"".join(srows) or b"\0" * _RULE.size, dtype=np.uint8).copy()
@@ -197,8 +231,10 @@ _COMB = {"add": 0, "mul": 1}
 def wide_eligible(conv: DatumToFvConverter) -> bool:
     """configs the wide native / GPU converter reproduces exactly: str /
     space / ngram splitters, every sample and global weight, num / log num
-    types, add / mul combinations; no filters, plug-ins or regex matchers"""
-    if conv.string_filters or conv.num_filters or conv.binary_rules:
+    types, add / mul combinations; num filters where the fixed-slot path
+    takes them (built-in method, non-regex key, up to MAX_FILTER_CHAINS
+    chains); no string filters, plug-ins or regex matchers"""
+    if conv.string_filters or conv.binary_rules or not _filters_ok(conv):
         return False
     for r in conv.string_rules:
         if r.split_kind not in _SPLIT or r.matcher.kind not in _KIND:
@@ -217,36 +253,28 @@ def wide_eligible(conv: DatumToFvConverter) -> bool:
 
 
 class WideRuleTable:
-    """Packed wide rule tables: string rules, num rules, combination rules
-    (two entries each: left matcher + "/type" suffix + op, right matcher)."""
+    """Packed wide rule tables: string rules, num rules (the base rows, then
+    the derived rows of the filter chains, packed by the helper GpuRuleTable
+    uses: ``n_base`` base rows, ``n_chains`` chains, ``n_nrules`` =
+    ``n_base * (1 + n_chains)``), combination rules (two entries each: left
+    matcher + "/type" suffix + op, right matcher)."""
 
     def __init__(self, conv: DatumToFvConverter):
         if not wide_eligible(conv):
             raise ValueError("converter config is not eligible for the wide native path")
         blob = bytearray()
-
-        def put(b: bytes) -> tuple[int, int]:
-            off = len(blob)
-            blob.extend(b)
-            return off, len(b)
-
         srows = []
         for r in conv.string_rules:
-            mo, ml = put(r.matcher.arg.encode())
-            so, sl = put(r.suffix.encode())
+            mo, ml = _put(blob, r.matcher.arg.encode())
+            so, sl = _put(blob, r.suffix.encode())
             vk = _SPLIT[r.split_kind] | _SW[r.sw] << 4 | _GW[r.gw] << 8
             srows.append(_RULE.pack(_KIND[r.matcher.kind], mo, ml, so, sl, vk, 0.0, r.split_n))
-        nrows = []
-        for r in conv.num_rules:
-            mo, ml = put(r.matcher.arg.encode())
-            so, sl = put(f"@{r.type_name}".encode())
-            nrows.append(_RULE.pack(_KIND[r.matcher.kind], mo, ml, so, sl,
-                                    1 if r.kind == "log" else 0, 0.0, 0))
+        nrows, self.n_base, self.n_chains = _pack_num_rows(conv, blob, lambda r: r.kind == "log")
         crows = []
         for ml_, mr_, tname, _ in conv.combination_rules:
-            lo, ll = put(ml_.arg.encode())
-            so, sl = put(f"/{tname}".encode())
-            ro, rl = put(mr_.arg.encode())
+            lo, ll = _put(blob, ml_.arg.encode())
+            so, sl = _put(blob, f"/{tname}".encode())
+            ro, rl = _put(blob, mr_.arg.encode())
             crows.append(_RULE.pack(_KIND[ml_.kind], lo, ll, so, sl,
                                     _COMB[conv.combination_methods[tname]], 0.0, 0))
             crows.append(_RULE.pack(_KIND[mr_.kind], ro, rl, 0, 0, 0, 0.0, 0))
@@ -264,6 +292,6 @@ class WideRuleTable:
 def gpu_eligible(conv: DatumToFvConverter) -> bool:
     """the GPU converts this config: the fixed-slot fast path (built-in num
     filters included) or the wide rule-set kernels (csrc/hip/fv_wide.hip:
-    ngram / space, tf / idf / bm25 with the DF table in HBM, combinations; no
-    filters)"""
+    ngram / space, tf / idf / bm25 with the DF table in HBM, combinations,
+    built-in num filters)"""
     return fast_eligible(conv) or wide_eligible(conv)

@@ -1,7 +1,8 @@
 """Device conversion for the wide rule set (csrc/hip/fv_wide.hip): ngram /
 space splitters, tf / log_tf sample weights, idf / bm25 global weights
-against a document-frequency table in HBM, num / log rules and add / mul
-combinations. Equal to the native host converter (csrc/native/
+against a document-frequency table in HBM, num / log rules, built-in num
+filters (derived rows of the num rule table, emitted chain block by chain
+block) and add / mul combinations. Equal to the native host converter (csrc/native/
 jb_hostfv_wide.hpp) and to the Python converter (tests/test_fv_wide.py).
 
 Global weights keep the converter's sequential semantics inside a batch:
@@ -103,7 +104,8 @@ class WideDevice:
         # which must not read its (not yet written) slots
         gw = torch.zeros(cap, dtype=torch.uint8, device=d)
         hip.fvw_emit(buf, buf_len, datum_off, datum_len, n, row_ptr, self.srules, rt.n_srules,
-                     self.nrules, rt.n_nrules, self.blob, self.H, idx, val, hs, names, gw, self.err)
+                     self.nrules, rt.n_nrules, rt.n_base, self.blob, self.H, idx, val, hs, names, gw,
+                     self.err)
         if self.df is not None:
             self._weigh(row_ptr, total, n, idx, val, gw, update)
         if rt.n_crules:

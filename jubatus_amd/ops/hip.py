@@ -147,7 +147,7 @@ _SIGS = {
     "jb_fvw_count": (_i32, [_c_void_p, _i64, _c_void_p, _c_void_p, _i32, _c_void_p, _i32, _c_void_p,
                             _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "jb_fvw_emit": (_i32, [_c_void_p, _i64, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _i32,
-                           _c_void_p, _i32, _c_void_p, _u64, _c_void_p, _c_void_p, _c_void_p,
+                           _c_void_p, _i32, _i32, _c_void_p, _u64, _c_void_p, _c_void_p, _c_void_p,
                            _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "jb_fvw_comb": (_i32, [_c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                            _i32, _c_void_p, _u64, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
@@ -282,15 +282,19 @@ def fvw_count(buf, buf_len: int, datum_off, datum_len, n: int, srules, ns: int, 
 
 
 def fvw_emit(buf, buf_len: int, datum_off, datum_len, n: int, row_ptr, srules, ns: int, nrules,
-             nn: int, blob, H: int, idx, val, hs, names, gw, err) -> None:
-    """wide converter, pass 2: base features into each datum's slot range"""
+             nn: int, nbase: int, blob, H: int, idx, val, hs, names, gw, err) -> None:
+    """wide converter, pass 2: base features into each datum's slot range;
+    nn num rule rows = nbase base rows x (1 + filter chains)"""
     total = int(row_ptr[n].item()) if n else 0
     if idx.numel() < total or val.numel() < total or hs.numel() < total or gw.numel() < total or \
             names.numel() < total * fvw_name_bytes():
         raise ValueError("fvw_emit: output shorter than the slot count")
+    if row_ptr.numel() < n + 1 or nrules.numel() < 32 * nn or \
+            (nn % nbase if nbase > 0 else nn):
+        raise ValueError("fvw_emit: bad rule table or row_ptr shape")
     rc = _fn("jb_fvw_emit")(_p(buf), buf_len, _p(datum_off), _p(datum_len), n, _p(row_ptr),
-                            _p(srules), ns, _p(nrules), nn, _p(blob), H, _p(idx), _p(val), _p(hs),
-                            _p(names), _p(gw), _p(err), _stream())
+                            _p(srules), ns, _p(nrules), nn, nbase, _p(blob), H, _p(idx), _p(val),
+                            _p(hs), _p(names), _p(gw), _p(err), _stream())
     _check(rc, "jb_fvw_emit")
 
 

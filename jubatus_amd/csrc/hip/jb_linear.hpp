@@ -74,6 +74,50 @@ __device__ __forceinline__ void addw(bf16_t* p, float d, uint32_t r) {
   }
 }
 
+// Both bf16 halves of one word in a single compare-and-swap, each half with
+// its own random bits.
+__device__ __forceinline__ void addw2(uint32_t* w, float dlo, float dhi, uint32_t rlo,
+                                      uint32_t rhi) {
+  uint32_t old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (;;) {
+    const uint32_t lo = f_bf16_sr(bf16_f(old & 0xffffu) + dlo, rlo);
+    const uint32_t hi = f_bf16_sr(bf16_f(old >> 16) + dhi, rhi);
+    const uint32_t nw = (hi << 16) | lo;
+    if (nw == old) return;
+    const uint32_t seen = atomicCAS(w, old, nw);
+    if (seen == old) return;
+    old = seen;
+    rlo = jb_mix32(rlo, seen);
+    rhi = jb_mix32(rhi, seen);
+  }
+}
+
+// addw in the paired lane layout of the atomic update: lanes 2j and 2j+1
+// carry the y and lstar elements of one row and issue together, so the two
+// adds of a row whose labels share a 64-byte segment (always at label
+// capacities <= 16) leave as one memory-side request instead of two. Every
+// lane of the wave calls it (`on`: the lane has an element). On a bf16 table
+// with `same_word` (wave-uniform: y ^ 1 == lstar, so both lanes `on`) the two
+// elements are the halves of one 32-bit word and two swaps would fight over
+// it; the even lane then swaps both halves at once.
+__device__ __forceinline__ void addw_pair(float* p, float d, uint32_t, bool on, bool, int) {
+  if (on) atomicAdd(p, d);
+}
+__device__ __forceinline__ void addw_pair(bf16_t* p, float d, uint32_t r, bool on, bool same_word,
+                                          int lane) {
+  if (same_word) {
+    const float d1 = __shfl_xor(d, 1, 64);
+    const uint32_t r1 = (uint32_t)__shfl_xor((int)r, 1, 64);
+    if (on && !(lane & 1)) {
+      const bool hi = ((uintptr_t)p & 2) != 0;
+      addw2(reinterpret_cast<uint32_t*>((uintptr_t)p & ~(uintptr_t)3), hi ? d1 : d, hi ? d : d1,
+            hi ? r1 : r, hi ? r : r1);
+    }
+  } else if (on) {
+    addw(p, d, r);
+  }
+}
+
 enum Method : int { PERCEPTRON = 0, PA = 1, PA1 = 2, PA2 = 3, CW = 4, AROW = 5, NHERD = 6 };
 // kSerial: several streams with the result of applying them one after the
 // other (serial.hip: speculative scoring + an ordered committer)
@@ -259,18 +303,53 @@ __device__ __forceinline__ bool general_sample(const int32_t* __restrict__ fidx,
   nrm = wave_sum(nrm);
   float tau = 0.f, beta = 0.f;
   if (!step_coeffs(method, margin, var, nrm, lstar >= 0, C, &tau, &beta)) return false;
-  for (int base = 0; base < n; base += 64) {
-    const int j = base + lane;
-    if (j >= n) continue;
-    const int32_t idx = fidx[beg + j];
-    if (idx < 0) continue;
-    const float x = fval[beg + j];
-    const int64_t row = (int64_t)idx * LC;
-    const float a = use_s ? 1.f / ld_agent(P + row + y) : 1.f;
-    const float b = (use_s && lstar >= 0) ? 1.f / ld_agent(P + row + lstar) : 1.f;
-    apply_feature<LC, kAtomic>(W, P, idx, x, y, lstar, use_s, method, tau, beta, a, b, 0.f, 0.f,
-                               (uint32_t)beg);
-    if (touched != nullptr) touched[idx] = 1;
+  if constexpr (LC <= 64) {
+    // Paired lanes (see addw_pair): lane 2j carries (feature j, y), lane 2j+1
+    // (feature j, lstar), 32 features per instruction. The confidences of 64
+    // features are read before any of their adds, as in the lane-per-feature
+    // form below, and every element gets the same step and the same random
+    // bits. Rows wider than one 64-byte segment (LC > 64) would save no
+    // request and keep that form.
+    const int h = lane & 1;
+    const int lab = h ? lstar : y;
+    const bool lab_on = h == 0 || lstar >= 0;
+    const float t = h ? -tau : tau;
+    const bool same_word = sizeof(WT) == 2 && lstar >= 0 && (y ^ 1) == lstar;
+    for (int base = 0; base < n; base += 64) {
+      int64_t el[2];
+      float xs[2], inv[2];
+      bool on[2];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int j = base + 32 * k + (lane >> 1);
+        const int32_t idx = j < n ? fidx[beg + j] : -1;
+        on[k] = idx >= 0 && lab_on;
+        xs[k] = on[k] ? fval[beg + j] : 0.f;
+        el[k] = on[k] ? (int64_t)idx * LC + lab : 0;
+        inv[k] = (use_s && on[k]) ? 1.f / ld_agent(P + el[k]) : 1.f;
+        if (touched != nullptr && idx >= 0 && h == 0) touched[idx] = 1;
+      }
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const float dw = use_s ? t * inv[k] * xs[k] : t * xs[k];
+        addw_pair(W + el[k], dw, jb_mix32((uint32_t)el[k], (uint32_t)beg), on[k], same_word, lane);
+        if (use_s && on[k]) atomicAdd(P + el[k], dprec(method, beta, xs[k], inv[k]));
+      }
+    }
+  } else {
+    for (int base = 0; base < n; base += 64) {
+      const int j = base + lane;
+      if (j >= n) continue;
+      const int32_t idx = fidx[beg + j];
+      if (idx < 0) continue;
+      const float x = fval[beg + j];
+      const int64_t row = (int64_t)idx * LC;
+      const float a = use_s ? 1.f / ld_agent(P + row + y) : 1.f;
+      const float b = (use_s && lstar >= 0) ? 1.f / ld_agent(P + row + lstar) : 1.f;
+      apply_feature<LC, kAtomic>(W, P, idx, x, y, lstar, use_s, method, tau, beta, a, b, 0.f, 0.f,
+                                 (uint32_t)beg);
+      if (touched != nullptr) touched[idx] = 1;
+    }
   }
   return true;
 }

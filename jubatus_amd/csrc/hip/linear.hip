@@ -491,7 +491,10 @@ __global__ __launch_bounds__(64 * NW) void linear_train_pipe_kernel(
     int lstar = -1;
     float dwy = 0.f, dwl = 0.f, dpy = 0.f, dpl = 0.f, py = 1.f, pl = 1.f, wy = 0.f, wl = 0.f;
     float tau_s = 0.f;
-    bool ser = false, p_done = false;   // serialized confidence (atomic mode), P applied
+    bool ser = false;                   // serialized confidence (atomic mode)
+    bool on_p = false;                  // paired layout (atomic mode): this lane's
+    int64_t el_p = 0;                   // table element and its W step
+    float dw_p = 0.f;
     const bool mine = lane < n_s && idx_s >= 0;
     if (valid_s) ++n_valid;
     if (general_s) {
@@ -575,23 +578,64 @@ __global__ __launch_bounds__(64 * NW) void linear_train_pipe_kernel(
       // One stream is unaffected: its returned P is the value it gathered.
       // Rows repeated inside the sample keep the gathered value (the
       // reference applies a sample's features against the pre-sample state).
-      // Cost: one returning atomic per updated feature on the sample chain;
-      // the worst case (every sample updates) runs ~10% slower end to end,
-      // data with few updates is unchanged (profiles/r02_serialized_confidence.jsonl).
-      if (MODE == kAtomic && use_s && upd) {
-        bool dup = false;
-        for (int j = 0; j < n_s; ++j) {
-          const int32_t ij = __builtin_amdgcn_readlane(idx_s, j);
-          dup |= mine && j != lane && ij == idx_s;
+      // Paired lanes: the table rows of an atomic-mode update are written in
+      // a second lane layout, lane 2j = (feature j, y_s) and lane 2j+1 =
+      // (feature j, lstar) (odd lanes off without a wrong label; a staged
+      // sample has at most 32 features). idx, x and the precision increments
+      // move there with wave shuffles, so the returning P add of a sample is
+      // one instruction for both labels, and so is the W add in step 5. The
+      // two elements of a row then sit in adjacent lanes, and where they
+      // share a 64-byte segment (always at LC <= 16, where a row is one
+      // segment) they can leave as one memory-side request instead of two.
+      // Each lane gets the old value of its own element; the steps go back
+      // to lane j for the forwarding into s+1.
+      // Cost: one returning atomic instruction per updating sample on the
+      // sample chain. Requests to one line serialise (tens of ns each), so a
+      // row that every stream updates bounds the worst case (every sample
+      // updates); data with few updates does not notice
+      // (profiles/r02_serialized_confidence.jsonl, docs/PERFORMANCE.md
+      // "Paired atomics").
+      if (MODE == kAtomic && upd) {
+        if (use_s) {
+          bool dup = false;
+          for (int j = 0; j < n_s; ++j) {
+            const int32_t ij = __builtin_amdgcn_readlane(idx_s, j);
+            dup |= mine && j != lane && ij == idx_s;
+          }
+          tau_s = tau;
+          ser = mine && !dup;
         }
-        tau_s = tau;
-        ser = mine && !dup;
-        // (rows of the hot-row replica are serialized in LDS at apply time)
-        if (ser && !(HOT && hs_s >= 0)) {
-          const int64_t row = (int64_t)idx_s * LC;
-          dwy = tau * x_s / atomicAdd(P + row + y_s, dpy);
-          if (lstar >= 0) dwl = -tau * x_s / atomicAdd(P + row + lstar, dpl);
-          p_done = true;
+        // (rows of the hot-row replica are applied in LDS in step 5)
+        const bool tbl = mine && !(HOT && hs_s >= 0);
+        const int pj = lane >> 1;
+        const bool odd = (lane & 1) != 0;
+        const int fl = __shfl((tbl ? 1 : 0) | (ser ? 2 : 0), pj, 64);
+        const int32_t idx_p = __shfl(idx_s, pj, 64);
+        const float x_p = __shfl(x_s, pj, 64);
+        const float t_p = odd ? -tau : tau;
+        on_p = (fl & 1) && (!odd || lstar >= 0);
+        el_p = on_p ? (int64_t)idx_p * LC + (odd ? lstar : y_s) : 0;
+        dw_p = t_p * x_p;
+        if (use_s) {
+          const float py_p = __shfl(dpy, pj, 64);
+          const float pl_p = __shfl(dpl, pj, 64);
+          const float dp_p = odd ? pl_p : py_p;
+          // a repeated row steps with the gathered confidence
+          if (__builtin_amdgcn_ballot_w64(tbl && !ser)) {
+            const float gy = __shfl(dwy, pj, 64);
+            const float gl = __shfl(dwl, pj, 64);
+            dw_p = odd ? gl : gy;
+          }
+          if (on_p) {
+            const float p_old = atomicAdd(P + el_p, dp_p);
+            if (fl & 2) dw_p = t_p * x_p / p_old;
+          }
+          const float sy_j = __shfl(dw_p, 2 * lane, 64);
+          const float sl_j = __shfl(dw_p, 2 * lane + 1, 64);
+          if (ser && tbl) {
+            dwy = sy_j;
+            if (lstar >= 0) dwl = sl_j;
+          }
         }
       }
     }
@@ -653,6 +697,10 @@ __global__ __launch_bounds__(64 * NW) void linear_train_pipe_kernel(
       }
       dwy += cy; dwl += cl; dpy += qy; dpl += ql;
     }
+    if (MODE == kAtomic && upd) {  // table rows, paired lanes (P went first in step 3)
+      const bool same_word = sizeof(WT) == 2 && lstar >= 0 && (y_s ^ 1) == lstar;
+      addw_pair(W + el_p, dw_p, jb_mix32((uint32_t)el_p, (uint32_t)s), on_p, same_word, lane);
+    }
     if (upd && mine && !skip) {
       if (HOT && hs_s >= 0) {
         const int hb = hs_s * LC;
@@ -678,17 +726,10 @@ __global__ __launch_bounds__(64 * NW) void linear_train_pipe_kernel(
           atomicAdd(&hA[0][hb + lstar], dwl);
         }
       } else {
-        const int64_t row = (int64_t)idx_s * LC;
-        const uint32_t ry = jb_mix32((uint32_t)(row + y_s), (uint32_t)s);
-        const uint32_t rl = jb_mix32((uint32_t)(row + lstar), (uint32_t)s);
-        if (MODE == kAtomic) {
-          addw(W + row + y_s, dwy, ry);
-          if (lstar >= 0) addw(W + row + lstar, dwl, rl);
-          if (use_s && !p_done) {
-            atomicAdd(P + row + y_s, dpy);
-            if (lstar >= 0) atomicAdd(P + row + lstar, dpl);
-          }
-        } else {
+        if (MODE != kAtomic) {
+          const int64_t row = (int64_t)idx_s * LC;
+          const uint32_t ry = jb_mix32((uint32_t)(row + y_s), (uint32_t)s);
+          const uint32_t rl = jb_mix32((uint32_t)(row + lstar), (uint32_t)s);
           stw(W + row + y_s, wy + dwy, ry);
           if (lstar >= 0) stw(W + row + lstar, wl + dwl, rl);
           if (use_s) {

@@ -9,7 +9,10 @@ Each variant also runs with the hot-row LDS replica off (``nohot``) and on:
 the replica is what removes the hot-row atomic contention
 (csrc/hip/hot.hip, linear.hip "Hot rows").
 
-Usage: python tools/bench_train_kernel.py [--iters N] [--only SUBSTR]
+``--labels N`` sets the label count (default 16; 20 and 40 give the label
+capacities 32 and 64).
+
+Usage: python tools/bench_train_kernel.py [--iters N] [--only SUBSTR] [--labels N]
 """
 from __future__ import annotations
 
@@ -46,6 +49,7 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="", help="run the variants whose name contains this")
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--labels", type=int, default=16, help="label count of the generated data")
     args = ap.parse_args()
     import torch
 
@@ -73,14 +77,14 @@ def main() -> None:
     for name, mode, nreq, per, ns, nn, hot in variants:
         if args.only and args.only not in name:
             continue
-        bodies = make(random.Random(1), nreq, per, 16, ns, nn, 100000, hot)
+        bodies = make(random.Random(1), nreq, per, args.labels, ns, nn, 100000, hot)
         for use_hot in (False, True):
             if use_hot and mode == "exact":
                 continue
             clf = LinearClassifier("AROW", {"regularization_weight": 1.0}, DatumToFvConverter(conv),
                                    device=dev, concurrent_update=mode if mode != "exact" else "atomic")
             clf.hot_rows = use_hot
-            for y in range(16):
+            for y in range(args.labels):
                 clf.set_label(f"label{y}")
             b = clf.pipe.from_requests(bodies, True, clf.labels)
             clf._sync_labels()
@@ -104,7 +108,8 @@ def main() -> None:
             us = e0.elapsed_time(e1) * 1e3 / args.iters
             st2 = clf.train_stats()
             nsamp = nreq * per
-            rec = {"variant": name + (" hot" if use_hot else " nohot"), "first_us": round(first_us, 1),
+            rec = {"variant": name + (" hot" if use_hot else " nohot"), "labels": args.labels,
+                   "label_capacity": clf.LC, "first_us": round(first_us, 1),
                    "first_update_fraction": round((st1["updated"] - st0["updated"]) / nsamp, 3),
                    "us_per_launch": round(us, 1), "samples": nsamp,
                    "update_fraction": round((st2["updated"] - st1["updated"]) / nsamp / args.iters, 3),

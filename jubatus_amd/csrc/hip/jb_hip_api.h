@@ -203,6 +203,12 @@ int jb_nn_reduce(const float* dist, const int32_t* row, int nq, int k, const flo
                  int nrows, int mode, float alpha, float* out, int32_t* out_n,
                  hipStream_t stream);
 
+// nn_vote.hip
+// mode: 0 w = exp(-alpha d) (NN, euclidean), 1 w = 1 - d (cosine). row_lab:
+// the label id of every slot, -1 for none. out: [nq, nlabels], all written.
+int jb_nn_vote(const float* dist, const int32_t* row, int nq, int k, const int32_t* row_lab,
+               int nrows, int nlabels, int mode, float alpha, float* out, hipStream_t stream);
+
 // regression.hip
 // method: models/linear_oracle.py METHOD_IDS (Method of jb_linear.hpp). PA
 // launches regression_train_kernel, the other methods the templated

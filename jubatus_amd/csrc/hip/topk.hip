@@ -1520,14 +1520,17 @@ __global__ __launch_bounds__(kMergeStageT) void topk_merge_sorted_kernel(const f
     int wid = id;
     wave_argmin(wv, wid, lane);
     if (lane == 0) { s_rd[r] = wv; s_ri[r] = wid; }
-    if (v == wv && id == wid) {          // the owner (padding entries may match on several lanes: harmless)
+    if (v == wv && id == wid) {          // the owner (padding entries may match on several lanes)
 #pragma unroll
       for (int u = 0; u < L; ++u) {
         if (u != bu) continue;
         const int list = lane + 64 * u;
         const int p = ++pos[u];
-        hd[u] = p < k ? s_d[list * k + p] : INFINITY;
-        hi[u] = p < k ? s_i[list * k + p] : INT_MAX;
+        // (a lane past the last list matches a padding winner too: it has
+        // nothing staged to advance into and stays padding)
+        const bool more = list < nb && p < k;
+        hd[u] = more ? s_d[list * k + p] : INFINITY;
+        hi[u] = more ? s_i[list * k + p] : INT_MAX;
       }
     }
   }

@@ -89,6 +89,8 @@ _SIGS = {
                        _c_void_p, _c_void_p]),
     "jb_nn_reduce": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _c_void_p, _i32, _i32, _f32,
                             _c_void_p, _c_void_p, _c_void_p]),
+    "jb_nn_vote": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _c_void_p, _i32, _i32, _i32, _f32,
+                          _c_void_p, _c_void_p]),
     "jb_topk_blocks": (_i32, [_i64, _i32]),
     "jb_topk_mq_stats": (_i32, [_c_void_p]),
     "jb_topk_direct_scratch": (_i64, [_i32]),
@@ -491,6 +493,39 @@ def nn_reduce(dist, row, nq: int, k: int, targets, nrows: int, mode: int, alpha:
                              _p(out), _p(out_n), _stream())
     _check(rc, "jb_nn_reduce")
     return out, out_n
+
+
+NN_VOTE_MODES = {"distance": 0, "similarity": 1}
+
+
+def nn_vote(dist, row, nq: int, k: int, row_lab, nrows: int, nlabels: int, mode: int,
+            alpha: float, out=None):
+    """Label votes of the neighbours (csrc/hip/nn_vote.hip) over the [nq, k]
+    lists of topk_hamming / topk_scores (or a torch.topk of the same layout,
+    any k): -> out float32 [nq, nlabels], every element written. ``row_lab``:
+    int32, the label id of every slot (-1: none; an id outside [0, nlabels)
+    votes for nothing). ``mode``: a value of NN_VOTE_MODES; ``alpha`` is read
+    by mode 0 only. ``out``: a contiguous float32 tensor of at least nq *
+    nlabels elements to write into (a new one otherwise)."""
+    _dev(dist, torch.float32, "dist")
+    _dev(row, torch.int32, "row")
+    _dev(row_lab, torch.int32, "row_lab")
+    if mode not in (0, 1) or not 0.0 <= float(alpha) < math.inf:
+        raise ValueError("nn_vote: mode or alpha out of range")
+    if nq < 0 or k < 0 or nrows < 0 or nlabels <= 0:
+        raise ValueError("nn_vote: negative size or no label")
+    if dist.numel() < nq * k or row.numel() < nq * k or row_lab.numel() < nrows:
+        raise ValueError("nn_vote: bad operand shapes")
+    if out is None:
+        out = torch.empty((nq, nlabels), dtype=torch.float32, device=dist.device)
+    else:
+        _dev(out, torch.float32, "out")
+        if out.numel() < nq * nlabels:
+            raise ValueError("nn_vote: bad operand shapes")
+    rc = _fn("jb_nn_vote")(_p(dist), _p(row), nq, k, _p(row_lab), nrows, nlabels, mode,
+                           float(alpha), _p(out), _stream())
+    _check(rc, "jb_nn_vote")
+    return out
 
 
 def sparse_scan(qidx, qval, qnorm2: float, row_ptr, ridx, rval, rnorm2, valid, nrows: int,

@@ -223,6 +223,21 @@ int jb_regression_train_m(const int64_t* row_ptr, const int32_t* fidx, const flo
 int jb_regression_estimate(const int64_t* row_ptr, const int32_t* fidx, const float* fval, int n,
                            const float* W, float* out, hipStream_t stream);
 
+// regression_ordered.hip
+// Samples 0 .. n_samples-1 applied in index order by one workgroup (the
+// serial-equivalent training of a batch of requests laid out back to back),
+// every method of jb_regression_train_m with its operands. win_slots: slot
+// occurrences per LDS window, 0 for the default (4096); above the default:
+// hipErrorInvalidValue. status: two int32, [0] 0 on success, else a code and
+// [1] the index of the first sample that was not applied (codes in the
+// kernel's header). A bad method, a missing P for CW / AROW / NHERD or a
+// null status is hipErrorInvalidValue with nothing written; n_samples <= 0
+// launches nothing and returns 0.
+int jb_regression_train_ordered(const int64_t* row_ptr, const int32_t* fidx, const float* fval,
+                                const float* targets, int64_t n_samples, float* W, float* P,
+                                float* stats, float* slot_scratch, int method, float C, float eps,
+                                int win_slots, int32_t* status, hipStream_t stream);
+
 // scan.hip
 int jb_scan_train(const uint8_t* buf, const int64_t* req_off, const int64_t* req_len,
                   const int64_t* sample_base, int R, const uint64_t* lt_hash,

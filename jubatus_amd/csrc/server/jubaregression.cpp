@@ -23,7 +23,15 @@
 // train_requests); estimate batches are hashed the same way and scored by
 // jb_regression_estimate. Model files are byte-compatible with the Python
 // server's (models/regression.py pack()).
+//
+// JUBATUS_REGRESSION_UPDATE_MODE (atomic | exact, read once at start-up;
+// unset or anything else: atomic): in exact a batch of several requests is
+// trained by jb_regression_train_ordered (csrc/hip/regression_ordered.hip),
+// which applies the samples in request order, so the model is what the
+// requests leave behind one after the other. Its status word is read behind
+// the stream synchronisation; a nonzero word fails the batch's RPCs.
 #include <signal.h>
+#include <stdlib.h>
 #include <string.h>
 #include <time.h>
 #include <unistd.h>
@@ -139,8 +147,11 @@ class Regression : public jb::mix::Mixable {
   std::atomic<uint64_t> update_count{0}, train_calls{0}, train_batches{0};
 
   Regression(const Config& cfg, int device) : device_(device) {
+    const char* mode = getenv("JUBATUS_REGRESSION_UPDATE_MODE");
+    exact_ = mode != nullptr && strcmp(mode, "exact") == 0;
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
+    HIPCHK(hipMalloc((void**)&d_status_, 2 * sizeof(int32_t)));
     configure(cfg);
   }
 
@@ -192,6 +203,22 @@ class Regression : public jb::mix::Mixable {
     // d_scratch_: one float per slot, where the kernel parks the P
     // increments of samples wider than its register slots
     float* scratch = cfg_.cov ? d_scratch_.get(std::max<int64_t>(slots, 1)) : nullptr;
+    if (exact_ && ns > 1) {
+      // the requests lie back to back in request order: sample order is the serial order
+      int32_t st[2] = {0, 0};
+      const int rc = jb_regression_train_ordered(d_row_.p, d_idx_.p, d_val_.p, d_tgt_.p, n, w_, p_, stats_, scratch,
+                                                 cfg_.mid, cfg_.C, cfg_.eps, 0, d_status_, stream_);
+      if (rc != 0) throw std::runtime_error("jb_regression_train_ordered failed: " + std::to_string(rc));
+      HIPCHK(hipMemcpyAsync(st, d_status_, sizeof st, hipMemcpyDeviceToHost, stream_));
+      HIPCHK(hipStreamSynchronize(stream_));
+      if (st[0] != 0) {
+        samples_ += (uint64_t)st[1];
+        throw std::runtime_error("jb_regression_train_ordered stopped at sample " + std::to_string(st[1]) +
+                                 " of the batch (status " + std::to_string(st[0]) + ")");
+      }
+      samples_ += (uint64_t)n;
+      return;
+    }
     const int rc = jb_regression_train_m(d_row_.p, d_idx_.p, d_val_.p, d_tgt_.p, d_sp_.p, ns, w_, p_, stats_,
                                          scratch, cfg_.mid, cfg_.C, cfg_.eps, ns > 1 ? 1 : 0, stream_);
     if (rc != 0) throw std::runtime_error("jb_regression_train_m failed: " + std::to_string(rc));
@@ -536,6 +563,7 @@ class Regression : public jb::mix::Mixable {
     add("batching.train.calls", std::to_string(train_calls.load()));
     add("batching.train.launches", std::to_string(train_batches.load()));
     add("train.samples_trained", std::to_string(samples_));
+    add("train.update_mode", exact_ ? "exact" : "atomic");
     add("device", "cuda:" + std::to_string(device_));
     if (mixing_) {
       add("mix.mode", "dense");
@@ -624,6 +652,8 @@ class Regression : public jb::mix::Mixable {
   float* w_ = nullptr;
   float* p_ = nullptr;      // precision table of CW / AROW / NHERD, else null
   float* stats_ = nullptr;
+  bool exact_ = false;            // JUBATUS_REGRESSION_UPDATE_MODE=exact
+  int32_t* d_status_ = nullptr;   // status word of jb_regression_train_ordered
   uint64_t samples_ = 0;
   LinearConv conv_;
   HostVec<int32_t> idx_;

@@ -39,6 +39,14 @@ Storage: w[H] (hashed features), and P[H] for CW / AROW / NHERD, in HBM on a
 GPU, NumPy otherwise.
 MIX: all-reduce mean of w, of the precisions P (as the classifier mixes) and
 of the target statistics.
+
+Several requests submitted together (``train_requests``) on a GPU:
+``concurrent_update="atomic"`` (the default) trains every request as its own
+stream with float atomics, so with sensitivity > 0 the model depends on launch
+timing; ``"exact"`` leaves the model as if the requests had been applied one
+after the other (the reference under its model lock), by one launch of
+csrc/hip/regression_ordered.hip over the requests laid out back to back. One
+request, and the host backend, are sequential in either mode.
 """
 from __future__ import annotations
 
@@ -59,6 +67,7 @@ class RegressionConfigError(ValueError):
 
 
 METHODS = ("PA", "PA1", "PA2", "perceptron", "CW", "AROW", "NHERD")
+UPDATE_MODES = ("atomic", "exact")
 COVARIANCE_METHODS = ("CW", "AROW", "NHERD")
 
 
@@ -145,9 +154,13 @@ def _train_one_m(w, P, stats, idx, val, y, C, eps, method) -> None:
 
 class Regression:
     def __init__(self, method: str, parameter: dict | None, converter: DatumToFvConverter,
-                 device: Any = None):
+                 device: Any = None, concurrent_update: str = "atomic"):
         if method not in METHODS:
             raise RegressionConfigError(f"unsupported regression method: {method}")
+        if concurrent_update not in UPDATE_MODES:
+            raise RegressionConfigError("concurrent_update must be 'atomic' or 'exact'")
+        self.concurrent_update = concurrent_update
+        self._pending: list = []        # status words of ordered launches not checked yet
         p = dict(parameter or {})
         self.cov = method in COVARIANCE_METHODS
         self.eps = float(p.get("sensitivity", 0.1))
@@ -175,6 +188,7 @@ class Regression:
 
     def clear(self) -> None:
         with self._lock:
+            self._check_ordered()
             if self.gpu:
                 t = self.torch
                 self.w = t.zeros(self.H, dtype=t.float32, device=self.device)
@@ -227,8 +241,27 @@ class Regression:
                     train_one(self.w, self.stats, idx, val, s, self.C, self.eps, self.method, self.P)
         return len(items)
 
+    def _check_ordered(self) -> None:
+        """the status words of the ordered launches since the last check (a
+        device synchronisation when there are any); a launch that stopped
+        early raises here, on the first synchronising call behind it"""
+        if self._pending:
+            from ..ops import hip
+            pending, self._pending = self._pending, []
+            for st in pending:
+                hip.regression_ordered_check(st)
+
     def _launch(self, b, targets, stream_ptr, nstreams: int) -> None:
         from ..ops import hip
+        if nstreams > 1 and self.concurrent_update == "exact":
+            # the requests lie back to back in request order: sample order is the serial order
+            scratch = self.torch.empty_like(b.fval) if self.cov else None
+            self._pending.append(hip.regression_train_ordered(
+                b.row_ptr, b.fidx, b.fval, targets, b.n, self.w, self.stats, self.C, self.eps,
+                method=self.method, P=self.P, slot_scratch=scratch))
+            if len(self._pending) >= 64:
+                self._check_ordered()
+            return
         if self.method == "PA":
             hip.regression_train(b.row_ptr, b.fidx, b.fval, targets, stream_ptr, nstreams, self.w,
                                  self.stats, self.C, self.eps, concurrent=nstreams > 1)
@@ -246,6 +279,7 @@ class Regression:
             return []
         rows = [self.conv.hashed(self.conv.convert(d)) for d in ds]
         with self._lock:
+            self._check_ordered()
             if self.gpu:
                 from ..ops import hip
                 b = self.pipe.from_rows(rows, None)
@@ -261,6 +295,7 @@ class Regression:
 
     # ---------------------------------------------------------- persist/mix
     def _host(self) -> tuple[np.ndarray, np.ndarray]:
+        self._check_ordered()
         if self.gpu:
             return self.w.cpu().numpy(), self.stats.cpu().numpy().astype(np.float64)
         return self.w, self.stats
@@ -345,7 +380,8 @@ class Regression:
 
     def get_status(self) -> dict[str, str]:
         return {"num_features": str(self.H), "method": self.method,
-                "storage": "hbm" if self.gpu else "host"}
+                "storage": "hbm" if self.gpu else "host",
+                "train.update_mode": self.concurrent_update}
 
 
 PARegression = Regression      # the name from when PA was the only method

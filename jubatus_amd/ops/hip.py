@@ -75,6 +75,9 @@ _SIGS = {
                                      _i32, _c_void_p]),
     "jb_regression_estimate": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
                                       _c_void_p]),
+    "jb_regression_train_ordered": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64,
+                                           _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _f32,
+                                           _f32, _i32, _c_void_p, _c_void_p]),
     "jb_signature": (_i32, [_c_void_p, _c_void_p, _c_void_p, _i32, _i32, _u64, _i32, _c_void_p,
                             _c_void_p, _c_void_p]),
     "jb_hamming_scan": (_i32, [_c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64,
@@ -1137,6 +1140,88 @@ def regression_train(row_ptr, fidx, fval, targets, stream_ptr, nstreams: int, W,
                                       _p(slot_scratch), mid, float(C), float(eps),
                                       1 if concurrent else 0, _stream())
     _check(rc, "jb_regression_train_m")
+
+
+REGRESSION_ORDERED_WIN_SLOTS = 4096      # csrc/hip/regression_ordered.hip kWinSlots
+REGRESSION_ORDERED_ERRORS = {1: "the LDS row table took no more rows", 2: "row_ptr is not monotone",
+                             3: "a sample of more than 256 slots needs slot_scratch"}
+
+
+def regression_ordered_table_bits(win_slots: int = 0) -> int:
+    """log2 of the LDS table's entries for a window of ``win_slots`` slot
+    occurrences (0: the default): at least 64 and at least 2 * win_slots"""
+    win = int(win_slots) or REGRESSION_ORDERED_WIN_SLOTS
+    bits = 6
+    while (1 << bits) < 2 * win:
+        bits += 1
+    return bits
+
+
+def regression_ordered_home(idx: int, win_slots: int = 0) -> int:
+    """home position of row ``idx`` in the LDS table of
+    csrc/hip/regression_ordered.hip (its header has the function)"""
+    return ((int(idx) * 0x9E3779B1) & 0xFFFFFFFF) >> (32 - regression_ordered_table_bits(win_slots))
+
+
+def regression_train_ordered(row_ptr, fidx, fval, targets, n_samples: int, W, stats, C: float,
+                             eps: float, method: str = "PA", P=None, slot_scratch=None,
+                             win_slots: int = 0, status=None):
+    """samples 0 .. n_samples-1 applied in index order by one launch of
+    csrc/hip/regression_ordered.hip (one workgroup, LDS windows of
+    ``win_slots`` slot occurrences, 0: the default). Operands as
+    regression_train. -> ``status`` (int32[2] on the device, allocated here
+    unless given): [0] is 0 once the launch has run through, else
+    regression_ordered_check raises. Reading it synchronises, so the caller
+    chooses when."""
+    from ..models.linear_oracle import METHOD_IDS, USES_COVARIANCE
+    _dev(W, torch.float32, "W")
+    _dev(stats, torch.float32, "stats")
+    _dev(targets, torch.float32, "targets")
+    n_samples = int(n_samples)
+    if W.dim() != 1 or stats.numel() < 3 or n_samples < 0 or row_ptr.numel() < n_samples + 1 \
+            or targets.numel() < n_samples:
+        raise ValueError("regression_train_ordered: bad operand shapes")
+    if method not in METHOD_IDS:
+        raise ValueError(f"regression_train_ordered: unknown method {method}")
+    if not 0 <= int(win_slots) <= REGRESSION_ORDERED_WIN_SLOTS:
+        raise ValueError(f"regression_train_ordered: win_slots must be 0 .. "
+                         f"{REGRESSION_ORDERED_WIN_SLOTS}")
+    mid = METHOD_IDS[method]
+    if mid in USES_COVARIANCE:
+        if P is None:
+            raise ValueError(f"regression_train_ordered: {method} needs the precision table P")
+        _dev(P, torch.float32, "P")
+        if P.shape != W.shape:
+            raise ValueError("regression_train_ordered: P must have the shape of W")
+        if slot_scratch is not None:
+            _dev(slot_scratch, torch.float32, "slot_scratch")
+            if slot_scratch.numel() < fval.numel():
+                raise ValueError("regression_train_ordered: slot_scratch is shorter than fval")
+        elif n_samples > 0 and int((row_ptr[1:n_samples + 1] - row_ptr[:n_samples]).max()) > 256:
+            raise ValueError("regression_train_ordered: samples of more than 256 slots need "
+                             "slot_scratch")
+    else:
+        P = slot_scratch = None
+    if status is None:
+        status = torch.zeros(2, dtype=torch.int32, device=W.device)
+    _dev(status, torch.int32, "status")
+    if status.numel() < 2:
+        raise ValueError("regression_train_ordered: status holds two int32")
+    rc = _fn("jb_regression_train_ordered")(_p(row_ptr), _p(fidx), _p(fval), _p(targets), n_samples,
+                                            _p(W), _p(P), _p(stats), _p(slot_scratch), mid,
+                                            float(C), float(eps), int(win_slots), _p(status),
+                                            _stream())
+    _check(rc, "jb_regression_train_ordered")
+    return status
+
+
+def regression_ordered_check(status) -> None:
+    """raises unless the launch that wrote ``status`` applied every sample
+    (synchronises with it)"""
+    code, first = (int(v) for v in status[:2].tolist())
+    if code != 0:
+        raise RuntimeError(f"jb_regression_train_ordered stopped at sample {first}: "
+                           f"{REGRESSION_ORDERED_ERRORS.get(code, 'status %d' % code)}")
 
 
 def regression_estimate(row_ptr, fidx, fval, n: int, W, out) -> None:

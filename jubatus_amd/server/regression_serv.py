@@ -9,8 +9,14 @@ PA2, perceptron, CW, AROW, NHERD) run on the hashed-table driver
 driver over the row engine (models/nn_regression.py). The native
 jubaregression serves the linear methods only and hands the other three to
 this server.
+
+JUBATUS_REGRESSION_UPDATE_MODE (atomic | exact; unset or anything else:
+atomic) is the linear driver's ``concurrent_update``: how a batch of queued
+train requests is applied on a GPU (models/regression.py).
 """
 from __future__ import annotations
+
+import os
 
 import msgpack
 
@@ -18,7 +24,7 @@ from ..common.exceptions import ArgumentError
 from ..common.mprpc import split_params
 from ..framework.engine_serv import EngineServ
 from ..fv_converter.converter import DatumToFvConverter, device_hash_max_size
-from ..models.regression import Regression
+from ..models.regression import UPDATE_MODES, Regression
 
 NN_METHODS = ("NN", "cosine", "euclidean")
 
@@ -30,11 +36,12 @@ def build_regression(cfg: dict, device):
         return NNRegression(method, cfg.get("parameter"),
                             DatumToFvConverter(cfg.get("converter") or {}), device=device)
     # (any other name: Regression raises "unsupported regression method")
+    mode = os.environ.get("JUBATUS_REGRESSION_UPDATE_MODE", "atomic")
     return Regression(method, cfg.get("parameter"),
                       DatumToFvConverter(cfg.get("converter") or {},
                                          default_hash_max_size=(device_hash_max_size()
                                                                 if device is not None else None)),
-                      device=device)
+                      device=device, concurrent_update=mode if mode in UPDATE_MODES else "atomic")
 
 
 class RegressionServ(EngineServ):

@@ -82,6 +82,11 @@ def build_native(force: bool = False, nproc: int = 8) -> str:
     return NATIVE_SO
 
 
+# extra hipcc flags per kernel source: gmm_wide.hip is compiled without the
+# packed fp32 VALU forms (v_pk_{add,mul,fma}_f32), plain fp32 ops throughout
+HIP_FILE_FLAGS = {"gmm_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def build_hip(force: bool = False, nproc: int = 8) -> str:
     srcs = sorted(glob.glob(os.path.join(CSRC, "hip", "*.hip")))
     hdrs = sorted(glob.glob(os.path.join(CSRC, "hip", "*.h*")))
@@ -96,7 +101,7 @@ def build_hip(force: bool = False, nproc: int = 8) -> str:
         o = os.path.join(BUILD, "hip_" + os.path.basename(s) + ".o")
         objs.append(o)
         if force or _newer(o, [s] + hdrs):
-            jobs.append((o, [HIPCC, *flags, "-c", s, "-o", o]))
+            jobs.append((o, [HIPCC, *flags, *HIP_FILE_FLAGS.get(os.path.basename(s), []), "-c", s, "-o", o]))
     _compile_all(jobs, nproc)
     _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", HIP_SO, *objs])
     return HIP_SO

@@ -68,6 +68,15 @@ int jb_fvw_comb(const uint8_t* buf, int n, const int64_t* row_ptr, const int64_t
                 hipStream_t stream);
 int64_t jb_fvw_name_bytes();
 
+// gmm_wide.hip
+// GMM EM on the whole GPU for 1 <= k <= 1024, k * d <= 2^22 (jb_gmm_em's
+// operands plus a device workspace). jb_gmm_em_wide_work: the workspace in
+// bytes, 0 outside the range; jb_gmm_em_wide returns -2 there.
+int64_t jb_gmm_em_wide_work(int n, int d, int k);
+int jb_gmm_em_wide(const float* X, int n, int d, const float* w, float* C, float* var, float* pi,
+                   int k, int iters, int32_t* assign, void* work, int64_t work_bytes,
+                   hipStream_t stream);
+
 // hot.hip
 int jb_hot_detect(const int64_t* row_ptr, int n, const int32_t* fidx, int64_t max_slots,
                   int block_min, int min_count, int max_rows, int32_t* gkey, int32_t* gcnt,

@@ -782,7 +782,21 @@ class Clustering : public HostEngine {
       if (rc == -2) h2d(dc, C.data(), 4 * kk * D);
       h2d(dv, var.data(), 4 * kk * D);
       h2d(dp, pi.data(), 4 * kk);
-      rc = jb_gmm_em(dx, (int)n, (int)D, dw, dc, dv, dp, (int)kk, 50, da, st_);
+      // one workgroup while k x dims fits its LDS, the whole-GPU chain past
+      // it (JB_GMM_WIDE=1: the chain first, for A/B runs)
+      static const bool wide_first = [] {
+        const char* e = getenv("JB_GMM_WIDE");
+        return e != nullptr && e[0] == '1';
+      }();
+      auto em_wide = [&]() -> int {
+        const int64_t wb = jb_gmm_em_wide_work((int)n, (int)D, (int)kk);
+        if (wb == 0) return -2;
+        return jb_gmm_em_wide(dx, (int)n, (int)D, dw, dc, dv, dp, (int)kk, 50, da, dWork_.get((size_t)wb), wb, st_);
+      };
+      rc = wide_first ? em_wide() : -2;
+      if (rc == -2) rc = jb_gmm_em(dx, (int)n, (int)D, dw, dc, dv, dp, (int)kk, 50, da, st_);
+      if (rc == -2 && !wide_first) rc = em_wide();
+      if (prof_.on && rc == -2) fprintf(stderr, "cluster: gmm k %zu x dims %zu: EM on the host\n", kk, D);
       if (rc == -2) {
         if (lloyd_dev) {
           d2h(C.data(), dc, 4 * kk * D);
@@ -1041,6 +1055,7 @@ class Clustering : public HostEngine {
   Dev<float> dX_, dW_, dC_, dXn_, dCn_, dOut_, dScr_, dV_, dP_;
   Dev<double> dU_;
   Dev<int32_t> dI_, dA_;
+  Dev<uint8_t> dWork_;              // jb_gmm_em_wide's workspace
 
   // Copies through page-locked staging: from pageable memory the runtime
   // stages each copy through a buffer of its own and waits for it (27 such

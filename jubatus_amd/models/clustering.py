@@ -527,8 +527,11 @@ class Clustering:
             from ..ops import hip
             C = C.contiguous().clone()
             self._em_assign = torch.empty(X.shape[0], dtype=torch.int32, device=X.device)
-            if hip.gmm_em(X.contiguous(), w.contiguous(), C, var, pi, iters, self._em_assign):
-                return C, var, pi
+            Xc, wc = X.contiguous(), w.contiguous()
+            # one workgroup while k x d fits its LDS, the whole-GPU chain past it
+            for em in ((hip.gmm_em_wide, hip.gmm_em) if hip.gmm_wide_forced() else (hip.gmm_em, hip.gmm_em_wide)):
+                if em(Xc, wc, C, var, pi, iters, self._em_assign):
+                    return C, var, pi
         self._em_assign = None
         for _ in range(iters):
             r = torch.softmax(self._log_resp(X, C, var, pi), dim=1) * w[:, None]

@@ -162,6 +162,9 @@ _SIGS = {
                            _c_void_p, _c_void_p, _c_void_p]),
     "jb_gmm_em": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
                          _i32, _c_void_p, _c_void_p]),
+    "jb_gmm_em_wide_work": (_i64, [_i32, _i32, _i32]),
+    "jb_gmm_em_wide": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
+                              _i32, _c_void_p, _c_void_p, _i64, _c_void_p]),
     "jb_lloyd": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _f32, _f32,
                         _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "jb_sqdist_mfma": (_i32, [_c_void_p, _i64, _c_void_p, _i32, _i32, _c_void_p, _c_void_p,
@@ -376,6 +379,40 @@ def gmm_em(X: torch.Tensor, w: torch.Tensor, C: torch.Tensor, var: torch.Tensor,
     rc = _fn("jb_gmm_em")(_p(X), n, d, _p(w), _p(C), _p(var), _p(pi), k, iters, _p(assign), _stream())
     _check(rc, "jb_gmm_em")
     return True
+
+
+def gmm_em_wide(X: torch.Tensor, w: torch.Tensor, C: torch.Tensor, var: torch.Tensor, pi: torch.Tensor,
+                iters: int, assign: torch.Tensor | None = None) -> bool:
+    """gmm_em on the whole GPU (csrc/hip/gmm_wide.hip: a launch chain per
+    iteration, the M-step sums on the matrix cores) for k x d past one
+    workgroup's LDS: 1 <= k <= 1024, k * d <= 2^22. Same operands and results
+    as gmm_em. False outside that range (the caller keeps its own path)."""
+    for t, nm in ((X, "X"), (w, "w"), (C, "C"), (var, "var"), (pi, "pi")):
+        _dev(t, torch.float32, nm)
+    n, d = X.shape
+    k = C.shape[0]
+    if C.shape[1] != d or var.shape != C.shape or pi.numel() != k or w.numel() < n:
+        raise ValueError("gmm_em_wide: bad operand shapes")
+    if assign is not None:
+        _dev(assign, torch.int32, "assign")
+        if assign.numel() < n:
+            raise ValueError("gmm_em_wide: assign shorter than X")
+    if n >= 2**31 or d >= 2**31 or k >= 2**31:
+        return False
+    nbytes = int(_fn("jb_gmm_em_wide_work")(n, d, k))
+    if nbytes == 0:
+        return False
+    work = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
+    rc = _fn("jb_gmm_em_wide")(_p(X), n, d, _p(w), _p(C), _p(var), _p(pi), k, iters, _p(assign), _p(work), nbytes,
+                               _stream())
+    _check(rc, "jb_gmm_em_wide")
+    return True
+
+
+def gmm_wide_forced() -> bool:
+    """JB_GMM_WIDE=1: the callers of gmm_em try gmm_em_wide first, also for
+    shapes the one-workgroup kernel takes (A/B runs; off by default)"""
+    return os.environ.get("JB_GMM_WIDE", "") == "1"
 
 
 def signature(row_ptr, fidx, fval, n: int, hash_num: int, seed: int, mode: int, bits, norms) -> None:

@@ -77,6 +77,17 @@ int jb_gmm_em_wide(const float* X, int n, int d, const float* w, float* C, float
                    int k, int iters, int32_t* assign, void* work, int64_t work_bytes,
                    hipStream_t stream);
 
+// kmeans_wide.hip
+// Weighted Lloyd on the whole GPU for 1 <= k <= 1024, k * d <= 2^22 (jb_lloyd's
+// rule; C in place, assign required, done_iters may be null: the update
+// iterations run, the converging one included). jb_lloyd_wide_work: the device
+// workspace in bytes, 0 outside the range; jb_lloyd_wide returns -2 there. It
+// synchronises the stream between groups of 8 iterations.
+int64_t jb_lloyd_wide_work(int n, int d, int k);
+int jb_lloyd_wide(const float* X, int n, int d, const float* w, float* C, int k, int iters,
+                  float atol, float rtol, int32_t* assign, int32_t* done_iters, void* work,
+                  int64_t work_bytes, hipStream_t stream);
+
 // hot.hip
 int jb_hot_detect(const int64_t* row_ptr, int n, const int32_t* fidx, int64_t max_slots,
                   int block_min, int min_count, int max_rows, int32_t* gkey, int32_t* gcnt,

@@ -757,7 +757,22 @@ class Clustering : public HostEngine {
     h2d(dx, X.data(), 4 * n * D);
     h2d(dw, w.data(), 4 * n);
     h2d(dc, C.data(), 4 * kk * D);
-    int rc = jb_lloyd(dx, (int)n, (int)D, dw, dc, (int)kk, 100, 1e-6f, 1e-5f, da, nullptr, dd, st_);
+    // one workgroup while k x dims fits its LDS, the whole-GPU chain past it
+    // (JB_LLOYD_WIDE=1: the chain first, for A/B runs)
+    static const bool lloyd_wide_first = [] {
+      const char* e = getenv("JB_LLOYD_WIDE");
+      return e != nullptr && e[0] == '1';
+    }();
+    auto lloyd_wide = [&]() -> int {
+      const int64_t wb = jb_lloyd_wide_work((int)n, (int)D, (int)kk);
+      if (wb == 0) return -2;
+      return jb_lloyd_wide(dx, (int)n, (int)D, dw, dc, (int)kk, 100, 1e-6f, 1e-5f, da, dd, dWork_.get((size_t)wb), wb,
+                           st_);
+    };
+    int rc = lloyd_wide_first ? lloyd_wide() : -2;
+    if (rc == -2) rc = jb_lloyd(dx, (int)n, (int)D, dw, dc, (int)kk, 100, 1e-6f, 1e-5f, da, nullptr, dd, st_);
+    if (rc == -2 && !lloyd_wide_first) rc = lloyd_wide();
+    if (prof_.on && rc == -2) fprintf(stderr, "cluster: k %zu x dims %zu: Lloyd on the host\n", kk, D);
     const bool gmm = p_.method == "gmm";
     const bool lloyd_dev = rc != -2;    // Lloyd's centers are in dc
     if (prof_.on && gmm) {   // (kmeans: the Lloyd time includes the read-back below)
@@ -766,7 +781,7 @@ class Clustering : public HostEngine {
       t0 = Clock::now();
     }
     if (rc == -2) {
-      host_lloyd(X, w, n, D, kk, &C, &assign);   // k x dims beyond the kernel's LDS
+      host_lloyd(X, w, n, D, kk, &C, &assign);   // k x dims beyond both kernels' range
     } else {
       if (rc) throw std::runtime_error("jb_lloyd failed");
       if (!gmm) {   // GMM's EM starts from Lloyd's centers where they are (no round trip)
@@ -1055,7 +1070,7 @@ class Clustering : public HostEngine {
   Dev<float> dX_, dW_, dC_, dXn_, dCn_, dOut_, dScr_, dV_, dP_;
   Dev<double> dU_;
   Dev<int32_t> dI_, dA_;
-  Dev<uint8_t> dWork_;              // jb_gmm_em_wide's workspace
+  Dev<uint8_t> dWork_;              // jb_lloyd_wide's, then jb_gmm_em_wide's workspace
 
   // Copies through page-locked staging: from pageable memory the runtime
   // stages each copy through a buffer of its own and waits for it (27 such

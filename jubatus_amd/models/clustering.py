@@ -485,7 +485,13 @@ class Clustering:
         if X.is_cuda:
             from ..ops import hip
             C = C.contiguous()
-            fused = hip.lloyd(X.contiguous(), w.contiguous(), C, 100, 1e-6, 1e-5)
+            Xc, wc = X.contiguous(), w.contiguous()
+            # one workgroup while k x d fits its LDS, the whole-GPU chain past it
+            for ll in ((hip.lloyd_wide, hip.lloyd) if hip.lloyd_wide_forced() else (hip.lloyd, hip.lloyd_wide)):
+                fused = ll(Xc, wc, C, 100, 1e-6, 1e-5)
+                if fused is not None:
+                    break
+        self._lloyd_iters = fused[1] if fused is not None else None
         for _ in range(0 if fused is not None else 100):
             a = self._sqdist(X, C).argmin(1)
             wsum = torch.zeros(C.shape[0], dtype=torch.float32, device=X.device).index_add_(0, a, w)

@@ -167,6 +167,9 @@ _SIGS = {
                               _i32, _c_void_p, _c_void_p, _i64, _c_void_p]),
     "jb_lloyd": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _f32, _f32,
                         _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "jb_lloyd_wide_work": (_i64, [_i32, _i32, _i32]),
+    "jb_lloyd_wide": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32, _i32, _f32, _f32,
+                             _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p]),
     "jb_sqdist_mfma": (_i32, [_c_void_p, _i64, _c_void_p, _i32, _i32, _c_void_p, _c_void_p,
                               _c_void_p, _c_void_p]),
     "jb_argmin_rows": (_i32, [_c_void_p, _i64, _i32, _c_void_p, _c_void_p]),
@@ -356,6 +359,40 @@ def lloyd(X: torch.Tensor, w: torch.Tensor, C: torch.Tensor, iters: int, atol: f
                          _p(done), _stream())
     _check(rc, "jb_lloyd")
     return assign, int(done.item())
+
+
+def lloyd_wide(X: torch.Tensor, w: torch.Tensor, C: torch.Tensor, iters: int, atol: float,
+               rtol: float):
+    """lloyd on the whole GPU (csrc/hip/kmeans_wide.hip: two launches an
+    iteration, scores and update sums on the matrix cores) for k x d past one
+    workgroup's LDS: 1 <= k <= 1024, k * d <= 2^22. Same operands and rule as
+    lloyd -> (assignment [n] device int32, update iterations run), or None
+    outside that range. Synchronises the stream every 8 iterations."""
+    _dev(X, torch.float32, "X")
+    _dev(w, torch.float32, "w")
+    _dev(C, torch.float32, "C")
+    n, d = X.shape
+    k = C.shape[0]
+    if C.shape[1] != d or w.numel() < n:
+        raise ValueError("lloyd_wide: bad operand shapes")
+    if n >= 2**31 or d >= 2**31 or k >= 2**31:
+        return None
+    nbytes = int(_fn("jb_lloyd_wide_work")(n, d, k))
+    if nbytes == 0:
+        return None
+    work = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
+    assign = torch.empty(n, dtype=torch.int32, device=X.device)
+    done = torch.empty(1, dtype=torch.int32, device=X.device)
+    rc = _fn("jb_lloyd_wide")(_p(X), n, d, _p(w), _p(C), k, iters, atol, rtol, _p(assign), _p(done),
+                              _p(work), nbytes, _stream())
+    _check(rc, "jb_lloyd_wide")
+    return assign, int(done.item())
+
+
+def lloyd_wide_forced() -> bool:
+    """JB_LLOYD_WIDE=1: the callers of lloyd try lloyd_wide first, also for
+    shapes the one-workgroup kernel takes (A/B runs; off by default)"""
+    return os.environ.get("JB_LLOYD_WIDE", "") == "1"
 
 
 def gmm_em(X: torch.Tensor, w: torch.Tensor, C: torch.Tensor, var: torch.Tensor, pi: torch.Tensor,

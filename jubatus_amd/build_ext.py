@@ -84,6 +84,7 @@ def build_native(force: bool = False, nproc: int = 8) -> str:
 
 # extra hipcc flags per kernel source: gmm_wide.hip is compiled without the
 # packed fp32 VALU forms (v_pk_{add,mul,fma}_f32), plain fp32 ops throughout
+# (jb_slab.hpp, the layer the two files share, is included from them only)
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_FILE_FLAGS = {"gmm_wide.hip": _NO_PK_F32,
                   "kmeans_wide.hip": _NO_PK_F32}   # its sums must keep one fixed fp32 order, as gmm_wide's

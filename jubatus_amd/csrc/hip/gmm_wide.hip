@@ -32,87 +32,34 @@
 // in place (one wave per row, max and sum by DPP / permlane).
 //
 // M-step: S1, S2 and nk are true GEMMs over the points with no cancellation,
-// so they run on v_mfma_f32_16x16x4_f32 (fragment maps at the top of
-// clustering.hip): A = R^T from sR, lane l holds R[i0 + (l >> 4)][j0 + (l & 15)];
-// B = the X tile, lane l holds X[i0 + (l >> 4)][q0 + (l & 15)], its square for
-// S2 and a column of ones for nk; a step covers 4 points. A wave owns the
-// (16 components x 16 dims) tiles wave, wave + 4, ... of a chunk, and the lane
-// that holds an output element is the only writer of that element of the
-// workgroup's partial: a plain store for the first slab, read-add-write after
-// it. No float atomics.
+// so they run on the matrix cores into the workgroup's own partial, as in
+// jb_slab.hpp (update_sums with the squares).
 #include <stdlib.h>
 
-#include "jb_device.hpp"
 #include "jb_hip_api.h"
+#include "jb_slab.hpp"
 
 namespace jb {
 namespace gw {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace jb::slab;   // kT, kDC, Geo, block_sum, stage_x, update_sums: as in jb_slab.hpp
 
-constexpr int kT = 256;              // threads of every kernel here
-constexpr int kDC = 32;              // dims per X chunk in LDS
-constexpr int kXS = 48;              // row stride of the X tile: rows i .. i + 3 on distinct banks
-constexpr int kMaxK = 1024;
-constexpr int64_t kMaxKD = (int64_t)1 << 22;
-constexpr int64_t kWorkCap = (int64_t)256 << 20;
-constexpr int kMaxGrid = 256;        // one workgroup a CU
-
-struct Geo {
-  int KP;        // k padded to the 16-component tile
-  int SP;        // points a slab
-  int RS;        // row stride of sR
-  int JT;        // E-step: threads along the components (a power of two), kT / JT point groups
-  int G;         // workgroups of the em kernel
-  int64_t PS;    // floats of one partial: S1 [k d] | S2 [k d] | nk [k]
-};
-
-// 0 in G: outside the supported range
+// one partial: S1 [k d] | S2 [k d] | nk [k]; the fixed part of the workspace: 1 / var [k d] | lc [k] | nk [k]
 __host__ inline Geo geometry(int64_t n, int64_t d, int64_t k) {
-  Geo g = {};
-  if (n < 1 || n > INT32_MAX || d < 1 || k < 1 || k > kMaxK || k * d > kMaxKD) return g;
-  g.KP = (int)((k + 15) / 16 * 16);
-  g.SP = g.KP <= 128 ? 64 : g.KP <= 384 ? 32 : 16;
-  g.RS = (g.KP + 47) / 64 * 64 + 16;             // RS % 64 == 16: 4 rows x 16 columns, 64 banks
-  g.JT = 1;
-  while (g.JT < k && g.JT < kT) g.JT <<= 1;
-  g.PS = 2 * k * d + k;
-  const int64_t fixed = k * d + 2 * k;            // 1 / var, lc, nk
-  const int64_t room = (kWorkCap / 4 - fixed) / g.PS;
-  const int64_t slabs = (n + g.SP - 1) / g.SP;
-  int64_t G = slabs < kMaxGrid ? slabs : kMaxGrid;
-  if (G > room) G = room;
-  g.G = (int)G;
-  return g;
+  return jb::slab::geometry(n, d, k, 2 * k * d + k, k * d + 2 * k);
 }
 
-__host__ inline size_t lds_bytes(const Geo& g) { return sizeof(float) * ((size_t)g.SP * g.RS + (size_t)g.SP * kXS); }
-
-// the block's sum in a fixed order, every thread gets it (red: 4 floats)
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  v = wave_sum_fast(v, lane);
-  __syncthreads();                   // (red may still be read from the previous call)
-  if (lane == 0) red[wv] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
+// E-step: threads along the components (a power of two), kT / JT point groups
+__host__ inline int estep_threads(int k) {
+  int JT = 1;
+  while (JT < k && JT < kT) JT <<= 1;
+  return JT;
 }
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
   return v;
-}
-
-// rows [row0, row0 + SP) x dims [q0, q0 + kDC) of X into the LDS tile, zeros
-// past n and past d
-__device__ __forceinline__ void stage_x(float* __restrict__ sX, const float* __restrict__ X, int n, int d,
-                                        int64_t row0, int q0, int SP) {
-  for (int e = threadIdx.x; e < SP * kDC; e += kT) {
-    const int i = e / kDC, q = e - i * kDC;
-    const int64_t gi = row0 + i;
-    sX[i * kXS + q] = (gi < n && q0 + q < d) ? X[gi * d + q0 + q] : 0.f;
-  }
 }
 
 // ASSIGN: the E-step only, then every point's argmax (first index on ties)
@@ -122,14 +69,14 @@ __global__ __launch_bounds__(kT) void gmm_wide_em_kernel(const float* __restrict
                                                          const float* __restrict__ C,
                                                          const float* __restrict__ IV,
                                                          const float* __restrict__ LC, int k, Geo g,
-                                                         float* __restrict__ part,
+                                                         int JT, float* __restrict__ part,
                                                          int32_t* __restrict__ assign) {
   extern __shared__ float s_gw[];
   float* sR = s_gw;                                // [SP][RS]
   float* sX = sR + (size_t)g.SP * g.RS;            // [SP][kXS]
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int SP = g.SP, RS = g.RS, KP = g.KP;
-  const int jl = t & (g.JT - 1), ig = t / g.JT, IT = kT / g.JT;
+  const int jl = t & (JT - 1), ig = t / JT, IT = kT / JT;
   float* P1 = part + (int64_t)blockIdx.x * g.PS;
   float* P2 = P1 + (int64_t)k * d;
   float* Pn = P2 + (int64_t)k * d;
@@ -142,7 +89,7 @@ __global__ __launch_bounds__(kT) void gmm_wide_em_kernel(const float* __restrict
       __syncthreads();                             // the tile's last readers are done
       stage_x(sX, X, n, d, row0, q0, SP);
       __syncthreads();
-      for (int j = jl; j < k; j += g.JT) {
+      for (int j = jl; j < k; j += JT) {
         float c[kDC], iv[kDC];
         const float* cj = C + (int64_t)j * d + q0;
         const float* ivj = IV + (int64_t)j * d + q0;
@@ -215,39 +162,7 @@ __global__ __launch_bounds__(kT) void gmm_wide_em_kernel(const float* __restrict
     }
     if (ASSIGN) continue;
     // M-step partial sums of the slab on the matrix cores
-    const int jtiles = KP / 16;
-    for (int q0 = 0; q0 < d; q0 += kDC) {
-      __syncthreads();                             // sR complete / the tile's last readers are done
-      stage_x(sX, X, n, d, row0, q0, SP);
-      __syncthreads();
-      for (int tile = wv; tile < jtiles * (kDC / 16); tile += kT / 64) {
-        const int j0 = (tile / (kDC / 16)) * 16, qq0 = (tile % (kDC / 16)) * 16;
-        if (q0 + qq0 >= d) continue;               // (wave-uniform)
-        const bool with_nk = q0 + qq0 == 0;
-        f32x4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f}, a0 = {0.f, 0.f, 0.f, 0.f};
-        const float* ra = sR + (lane >> 4) * RS + j0 + (lane & 15);
-        const float* xb = sX + (lane >> 4) * kXS + qq0 + (lane & 15);
-        for (int i0 = 0; i0 < SP; i0 += 4) {
-          const float a = ra[i0 * RS];
-          const float b = xb[i0 * kXS];
-          a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, a1, 0, 0, 0);
-          a2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b * b, a2, 0, 0, 0);
-          if (with_nk) a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, 1.f, a0, 0, 0, 0);
-        }
-        const int q = q0 + qq0 + (lane & 15);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int j = j0 + (lane >> 4) * 4 + r;
-          if (j >= k) continue;
-          if (q < d) {
-            const int64_t e = (int64_t)j * d + q;
-            P1[e] = first ? a1[r] : P1[e] + a1[r];
-            P2[e] = first ? a2[r] : P2[e] + a2[r];
-          }
-          if (with_nk && (lane & 15) == 0) Pn[j] = first ? a0[r] : Pn[j] + a0[r];
-        }
-      }
-    }
+    update_sums<true, 0>(sR, sX, X, n, d, k, row0, SP, RS, KP, P1, P2, Pn, first, wv, lane);
     first = false;
   }
 }
@@ -329,28 +244,22 @@ extern "C" int jb_gmm_em_wide(const float* X, int n, int d, const float* w, floa
   float* NK = LC + k;
   float* part = NK + k;
   const size_t lds = lds_bytes(g);
+  const int JT = estep_threads(k);
   if (lds > 64 * 1024) {
-    static const hipError_t attr = [] {
-      hipError_t e = hipFuncSetAttribute((const void*)gmm_wide_em_kernel<false>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)gmm_wide_em_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024);
-      return e;
-    }();
+    const hipError_t attr = allow_large_lds<gmm_wide_em_kernel<false>, gmm_wide_em_kernel<true>>();
     if (attr != hipSuccess) return (int)attr;
   }
   hipLaunchKernelGGL(gmm_wide_consts_kernel<false>, dim3(k), dim3(kT), 0, stream, var, k, d, NK, pi, IV, LC);
   const unsigned rgrid = (unsigned)((kd + kT - 1) / kT);
   for (int it = 0; it < iters; ++it) {
-    hipLaunchKernelGGL(gmm_wide_em_kernel<false>, dim3(g.G), dim3(kT), lds, stream, X, n, d, w, C, IV, LC, k, g, part,
-                       nullptr);
+    hipLaunchKernelGGL(gmm_wide_em_kernel<false>, dim3(g.G), dim3(kT), lds, stream, X, n, d, w, C, IV, LC, k, g, JT,
+                       part, nullptr);
     hipLaunchKernelGGL(gmm_wide_reduce_kernel, dim3(rgrid), dim3(kT), 0, stream, part, g.G, g.PS, k, d, C, var, IV,
                        NK);
     hipLaunchKernelGGL(gmm_wide_consts_kernel<true>, dim3(k), dim3(kT), 0, stream, var, k, d, NK, pi, IV, LC);
   }
   if (assign != nullptr)
-    hipLaunchKernelGGL(gmm_wide_em_kernel<true>, dim3(g.G), dim3(kT), lds, stream, X, n, d, w, C, IV, LC, k, g, part,
-                       assign);
+    hipLaunchKernelGGL(gmm_wide_em_kernel<true>, dim3(g.G), dim3(kT), lds, stream, X, n, d, w, C, IV, LC, k, g, JT,
+                       part, assign);
   return (int)hipGetLastError();
 }

@@ -36,11 +36,10 @@
 //
 // Row arg-min: one wave a row, min and lowest index by DPP / permlane. The
 // wave then overwrites its row with w_i at the winner and 0 elsewhere, and
-// S = R^T X, nk = R^T 1 run on the MFMA as the M-step of gmm_wide.hip does:
-// the lane that holds an output element is the only writer of that element of
-// the workgroup's partial, a plain store for the first slab and read-add-write
-// after it. The one-hot GEMM does k times the additions of a scatter; it
-// costs what the scores cost, needs no atomics and fixes the order.
+// S = R^T X, nk = R^T 1 run on the MFMA into the workgroup's own partial, as
+// in jb_slab.hpp (update_sums without the squares). The one-hot GEMM does k
+// times the additions of a scatter; it costs what the scores cost, needs no
+// atomics and fixes the order.
 //
 // Convergence: the workspace holds {stopped, iterations, changed, ticket}.
 // Reduce blocks that see a change atomicOr `changed` (an integer atomic,
@@ -53,58 +52,20 @@
 // SYNCHRONISES THE STREAM (once per group that is not the last).
 #include <stdlib.h>
 
-#include "jb_device.hpp"
 #include "jb_hip_api.h"
+#include "jb_slab.hpp"
 
 namespace jb {
 namespace kw {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace jb::slab;   // kT, kDC, Geo, block_sum, stage_x, update_sums: as in jb_slab.hpp
 
-constexpr int kT = 256;              // threads of every kernel here
-constexpr int kDC = 32;              // dims per X chunk in LDS
-constexpr int kXS = 48;              // row stride of the X tile: rows i .. i + 3 on distinct banks
-constexpr int kMaxK = 1024;
-constexpr int64_t kMaxKD = (int64_t)1 << 22;
-constexpr int64_t kWorkCap = (int64_t)256 << 20;
-constexpr int kMaxGrid = 256;        // one workgroup a CU
 constexpr int kGroup = 8;            // iterations enqueued between two reads of the state
 constexpr int kState = 4;            // int32 words: stopped, iterations, changed, ticket
 
-struct Geo {
-  int KP;        // k padded to the 16-centre tile
-  int SP;        // points a slab: 64 / 32 / 16, so that a wave holds at most 16 score tiles
-  int RS;        // row stride of sR
-  int G;         // workgroups of the step kernel
-  int64_t PS;    // floats of one partial: S [k d] | nk [k]
-};
-
-// 0 in G: outside the supported range
+// one partial: S [k d] | nk [k]; the fixed part of the workspace: the state | |c_j|^2 [k]
 __host__ inline Geo geometry(int64_t n, int64_t d, int64_t k) {
-  Geo g = {};
-  if (n < 1 || n > INT32_MAX || d < 1 || k < 1 || k > kMaxK || k * d > kMaxKD) return g;
-  g.KP = (int)((k + 15) / 16 * 16);
-  g.SP = g.KP <= 128 ? 64 : g.KP <= 384 ? 32 : 16;
-  g.RS = (g.KP + 47) / 64 * 64 + 16;             // RS % 64 == 16: 4 rows x 16 columns, 64 banks
-  g.PS = k * d + k;
-  const int64_t room = (kWorkCap / 4 - kState - k) / g.PS;
-  const int64_t slabs = (n + g.SP - 1) / g.SP;
-  int64_t G = slabs < kMaxGrid ? slabs : kMaxGrid;
-  if (G > room) G = room;
-  g.G = (int)G;
-  return g;
-}
-
-__host__ inline size_t lds_bytes(const Geo& g) { return sizeof(float) * ((size_t)g.SP * g.RS + (size_t)g.SP * kXS); }
-
-// the block's sum in a fixed order, every thread gets it (red: 4 floats)
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  v = wave_sum_fast(v, lane);
-  __syncthreads();                   // (red may still be read from the previous call)
-  if (lane == 0) red[wv] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
+  return jb::slab::geometry(n, d, k, k * d + k, kState + k);
 }
 
 // |c_j|^2 of the block's centre, the same order wherever it is computed
@@ -127,17 +88,6 @@ __device__ __forceinline__ void wave_argmin(float& bv, int& bj, int lane) {
   take_min(bv, bj, dpp_f<kDppMirror>(bv), dpp_i<kDppMirror>(bj));
   take_min(bv, bj, partner16_f(bv, lane), partner16_i(bj, lane));
   take_min(bv, bj, partner32_f(bv, lane), partner32_i(bj, lane));
-}
-
-// rows [row0, row0 + SP) x dims [q0, q0 + kDC) of X into the LDS tile, zeros
-// past n and past d
-__device__ __forceinline__ void stage_x(float* __restrict__ sX, const float* __restrict__ X, int n, int d,
-                                        int64_t row0, int q0, int SP) {
-  for (int e = threadIdx.x; e < SP * kDC; e += kT) {
-    const int i = e / kDC, q = e - i * kDC;
-    const int64_t gi = row0 + i;
-    sX[i * kXS + q] = (gi < n && q0 + q < d) ? X[gi * d + q0 + q] : 0.f;
-  }
 }
 
 // C[j][q .. q + 3], zeros past k and past d; vec: rows of C are float4-aligned
@@ -264,37 +214,7 @@ __global__ __launch_bounds__(kT) void kmeans_wide_step_kernel(const float* __res
     }
     if (ASSIGN) continue;
     // update sums of the slab on the matrix cores: A = R^T from sR, B = the X tile
-    const int jtiles = KP / 16;
-    for (int q0 = 0; q0 < d; q0 += kDC) {
-      __syncthreads();                             // sR complete / the tile's last readers are done
-      stage_x(sX, X, n, d, row0, q0, SP);
-      __syncthreads();
-      for (int tile = wv; tile < jtiles * (kDC / 16); tile += kT / 64) {
-        const int j0 = (tile / (kDC / 16)) * 16, qq0 = (tile % (kDC / 16)) * 16;
-        if (q0 + qq0 >= d) continue;               // (wave-uniform)
-        const bool with_nk = q0 + qq0 == 0;
-        f32x4 a1 = {0.f, 0.f, 0.f, 0.f}, a0 = {0.f, 0.f, 0.f, 0.f};
-        const float* ra = sR + kq * RS + j0 + ar;
-        const float* xb = sX + kq * kXS + qq0 + ar;
-#pragma unroll 4
-        for (int i0 = 0; i0 < SP; i0 += 4) {
-          const float a = ra[i0 * RS];
-          a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xb[i0 * kXS], a1, 0, 0, 0);
-          if (with_nk) a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, 1.f, a0, 0, 0, 0);
-        }
-        const int q = q0 + qq0 + ar;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int j = j0 + kq * 4 + r;
-          if (j >= k) continue;
-          if (q < d) {
-            const int64_t e = (int64_t)j * d + q;
-            P1[e] = first ? a1[r] : P1[e] + a1[r];
-          }
-          if (with_nk && ar == 0) Pn[j] = first ? a0[r] : Pn[j] + a0[r];
-        }
-      }
-    }
+    update_sums<false, 4>(sR, sX, X, n, d, k, row0, SP, RS, KP, P1, nullptr, Pn, first, wv, lane);
     first = false;
   }
 }
@@ -377,14 +297,8 @@ extern "C" int jb_lloyd_wide(const float* X, int n, int d, const float* w, float
   float* part = CN2 + k;
   const size_t lds = lds_bytes(g);
   if (lds > 64 * 1024) {                           // (only the 16-point slabs get there)
-    static const hipError_t attr = [] {
-      hipError_t e = hipFuncSetAttribute((const void*)kmeans_wide_step_kernel<1, 16, false>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)kmeans_wide_step_kernel<1, 16, true>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      return e;
-    }();
+    const hipError_t attr =
+        allow_large_lds<kmeans_wide_step_kernel<1, 16, false>, kmeans_wide_step_kernel<1, 16, true>>();
     if (attr != hipSuccess) return (int)attr;
   }
   hipLaunchKernelGGL(kmeans_wide_init_kernel, dim3(k), dim3(kT), 0, stream, C, d, CN2, state);

@@ -679,6 +679,16 @@ class Clustering : public HostEngine {
   static double since_us(Clock::time_point t0) {
     return std::chrono::duration<double, std::micro>(Clock::now() - t0).count();
   }
+  // one workgroup while k x dims fits its LDS, the whole-GPU chain past it
+  // (the variable `env` at 1: the chain first, for A/B runs) -> the first rc
+  // that is not -2, a kernel's "outside my range"
+  template <class Narrow, class Wide>
+  static int narrow_or_wide(const char* env, Narrow narrow, Wide wide) {
+    const char* e = getenv(env);
+    const bool wide_first = e != nullptr && e[0] == '1';
+    const int rc = wide_first ? wide() : narrow();
+    return rc != -2 ? rc : wide_first ? narrow() : wide();
+  }
 
   void close_bucket(const PointSet& full) {
     static const bool prof_on = [] {
@@ -757,21 +767,15 @@ class Clustering : public HostEngine {
     h2d(dx, X.data(), 4 * n * D);
     h2d(dw, w.data(), 4 * n);
     h2d(dc, C.data(), 4 * kk * D);
-    // one workgroup while k x dims fits its LDS, the whole-GPU chain past it
-    // (JB_LLOYD_WIDE=1: the chain first, for A/B runs)
-    static const bool lloyd_wide_first = [] {
-      const char* e = getenv("JB_LLOYD_WIDE");
-      return e != nullptr && e[0] == '1';
-    }();
-    auto lloyd_wide = [&]() -> int {
-      const int64_t wb = jb_lloyd_wide_work((int)n, (int)D, (int)kk);
-      if (wb == 0) return -2;
-      return jb_lloyd_wide(dx, (int)n, (int)D, dw, dc, (int)kk, 100, 1e-6f, 1e-5f, da, dd, dWork_.get((size_t)wb), wb,
-                           st_);
-    };
-    int rc = lloyd_wide_first ? lloyd_wide() : -2;
-    if (rc == -2) rc = jb_lloyd(dx, (int)n, (int)D, dw, dc, (int)kk, 100, 1e-6f, 1e-5f, da, nullptr, dd, st_);
-    if (rc == -2 && !lloyd_wide_first) rc = lloyd_wide();
+    int rc = narrow_or_wide(
+        "JB_LLOYD_WIDE",
+        [&] { return jb_lloyd(dx, (int)n, (int)D, dw, dc, (int)kk, 100, 1e-6f, 1e-5f, da, nullptr, dd, st_); },
+        [&] {
+          const int64_t wb = jb_lloyd_wide_work((int)n, (int)D, (int)kk);
+          if (wb == 0) return -2;
+          return jb_lloyd_wide(dx, (int)n, (int)D, dw, dc, (int)kk, 100, 1e-6f, 1e-5f, da, dd,
+                               dWork_.get((size_t)wb), wb, st_);
+        });
     if (prof_.on && rc == -2) fprintf(stderr, "cluster: k %zu x dims %zu: Lloyd on the host\n", kk, D);
     const bool gmm = p_.method == "gmm";
     const bool lloyd_dev = rc != -2;    // Lloyd's centers are in dc
@@ -797,20 +801,14 @@ class Clustering : public HostEngine {
       if (rc == -2) h2d(dc, C.data(), 4 * kk * D);
       h2d(dv, var.data(), 4 * kk * D);
       h2d(dp, pi.data(), 4 * kk);
-      // one workgroup while k x dims fits its LDS, the whole-GPU chain past
-      // it (JB_GMM_WIDE=1: the chain first, for A/B runs)
-      static const bool wide_first = [] {
-        const char* e = getenv("JB_GMM_WIDE");
-        return e != nullptr && e[0] == '1';
-      }();
-      auto em_wide = [&]() -> int {
-        const int64_t wb = jb_gmm_em_wide_work((int)n, (int)D, (int)kk);
-        if (wb == 0) return -2;
-        return jb_gmm_em_wide(dx, (int)n, (int)D, dw, dc, dv, dp, (int)kk, 50, da, dWork_.get((size_t)wb), wb, st_);
-      };
-      rc = wide_first ? em_wide() : -2;
-      if (rc == -2) rc = jb_gmm_em(dx, (int)n, (int)D, dw, dc, dv, dp, (int)kk, 50, da, st_);
-      if (rc == -2 && !wide_first) rc = em_wide();
+      rc = narrow_or_wide(
+          "JB_GMM_WIDE", [&] { return jb_gmm_em(dx, (int)n, (int)D, dw, dc, dv, dp, (int)kk, 50, da, st_); },
+          [&] {
+            const int64_t wb = jb_gmm_em_wide_work((int)n, (int)D, (int)kk);
+            if (wb == 0) return -2;
+            return jb_gmm_em_wide(dx, (int)n, (int)D, dw, dc, dv, dp, (int)kk, 50, da, dWork_.get((size_t)wb), wb,
+                                  st_);
+          });
       if (prof_.on && rc == -2) fprintf(stderr, "cluster: gmm k %zu x dims %zu: EM on the host\n", kk, D);
       if (rc == -2) {
         if (lloyd_dev) {

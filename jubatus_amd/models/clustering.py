@@ -120,6 +120,13 @@ def _ranges(starts: np.ndarray, lens: np.ndarray) -> np.ndarray:
     return rep + np.arange(tot, dtype=np.int64)
 
 
+def _narrow_or_wide(narrow, wide, wide_first: bool, *args):
+    """one workgroup while k x d fits its LDS, the whole-GPU chain past it (wide_first: the chain first)"""
+    for kernel in ((wide, narrow) if wide_first else (narrow, wide)):
+        if res := kernel(*args):
+            return res
+
+
 class PointSet:
     """weighted points: w [m] float64, CSR rows (key int64, value float32)
     and the msgpack bytes of every point's datum"""
@@ -486,11 +493,7 @@ class Clustering:
             from ..ops import hip
             C = C.contiguous()
             Xc, wc = X.contiguous(), w.contiguous()
-            # one workgroup while k x d fits its LDS, the whole-GPU chain past it
-            for ll in ((hip.lloyd_wide, hip.lloyd) if hip.lloyd_wide_forced() else (hip.lloyd, hip.lloyd_wide)):
-                fused = ll(Xc, wc, C, 100, 1e-6, 1e-5)
-                if fused is not None:
-                    break
+            fused = _narrow_or_wide(hip.lloyd, hip.lloyd_wide, hip.lloyd_wide_forced(), Xc, wc, C, 100, 1e-6, 1e-5)
         self._lloyd_iters = fused[1] if fused is not None else None
         for _ in range(0 if fused is not None else 100):
             a = self._sqdist(X, C).argmin(1)
@@ -533,11 +536,9 @@ class Clustering:
             from ..ops import hip
             C = C.contiguous().clone()
             self._em_assign = torch.empty(X.shape[0], dtype=torch.int32, device=X.device)
-            Xc, wc = X.contiguous(), w.contiguous()
-            # one workgroup while k x d fits its LDS, the whole-GPU chain past it
-            for em in ((hip.gmm_em_wide, hip.gmm_em) if hip.gmm_wide_forced() else (hip.gmm_em, hip.gmm_em_wide)):
-                if em(Xc, wc, C, var, pi, iters, self._em_assign):
-                    return C, var, pi
+            if _narrow_or_wide(hip.gmm_em, hip.gmm_em_wide, hip.gmm_wide_forced(), X.contiguous(), w.contiguous(),
+                               C, var, pi, iters, self._em_assign):
+                return C, var, pi
         self._em_assign = None
         for _ in range(iters):
             r = torch.softmax(self._log_resp(X, C, var, pi), dim=1) * w[:, None]

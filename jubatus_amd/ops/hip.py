@@ -8,6 +8,7 @@ order naturally with torch ops and RCCL collectives.
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 import os
 import time
@@ -375,24 +376,21 @@ def lloyd_wide(X: torch.Tensor, w: torch.Tensor, C: torch.Tensor, iters: int, at
     k = C.shape[0]
     if C.shape[1] != d or w.numel() < n:
         raise ValueError("lloyd_wide: bad operand shapes")
-    if n >= 2**31 or d >= 2**31 or k >= 2**31:
+    work = _wide_work("jb_lloyd_wide_work", n, d, k, X.device)
+    if work is None:
         return None
-    nbytes = int(_fn("jb_lloyd_wide_work")(n, d, k))
-    if nbytes == 0:
-        return None
-    work = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
     assign = torch.empty(n, dtype=torch.int32, device=X.device)
     done = torch.empty(1, dtype=torch.int32, device=X.device)
     rc = _fn("jb_lloyd_wide")(_p(X), n, d, _p(w), _p(C), k, iters, atol, rtol, _p(assign), _p(done),
-                              _p(work), nbytes, _stream())
+                              _p(work), work.numel(), _stream())
     _check(rc, "jb_lloyd_wide")
     return assign, int(done.item())
 
 
-def lloyd_wide_forced() -> bool:
-    """JB_LLOYD_WIDE=1: the callers of lloyd try lloyd_wide first, also for
-    shapes the one-workgroup kernel takes (A/B runs; off by default)"""
-    return os.environ.get("JB_LLOYD_WIDE", "") == "1"
+def _wide_work(query: str, n: int, d: int, k: int, device) -> torch.Tensor | None:
+    """a whole-GPU chain's workspace, sized by its ``*_work`` entry; None outside the chain's range"""
+    nbytes = int(_fn(query)(n, d, k)) if max(n, d, k) < 2**31 else 0
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
 
 
 def gmm_em(X: torch.Tensor, w: torch.Tensor, C: torch.Tensor, var: torch.Tensor, pi: torch.Tensor,
@@ -434,22 +432,23 @@ def gmm_em_wide(X: torch.Tensor, w: torch.Tensor, C: torch.Tensor, var: torch.Te
         _dev(assign, torch.int32, "assign")
         if assign.numel() < n:
             raise ValueError("gmm_em_wide: assign shorter than X")
-    if n >= 2**31 or d >= 2**31 or k >= 2**31:
+    work = _wide_work("jb_gmm_em_wide_work", n, d, k, X.device)
+    if work is None:
         return False
-    nbytes = int(_fn("jb_gmm_em_wide_work")(n, d, k))
-    if nbytes == 0:
-        return False
-    work = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
-    rc = _fn("jb_gmm_em_wide")(_p(X), n, d, _p(w), _p(C), _p(var), _p(pi), k, iters, _p(assign), _p(work), nbytes,
-                               _stream())
+    rc = _fn("jb_gmm_em_wide")(_p(X), n, d, _p(w), _p(C), _p(var), _p(pi), k, iters, _p(assign), _p(work),
+                               work.numel(), _stream())
     _check(rc, "jb_gmm_em_wide")
     return True
 
 
-def gmm_wide_forced() -> bool:
-    """JB_GMM_WIDE=1: the callers of gmm_em try gmm_em_wide first, also for
+def _forced(name: str) -> bool:
+    """NAME=1: the callers of a one-workgroup kernel try its whole-GPU chain first, also for
     shapes the one-workgroup kernel takes (A/B runs; off by default)"""
-    return os.environ.get("JB_GMM_WIDE", "") == "1"
+    return os.environ.get(name, "") == "1"
+
+
+lloyd_wide_forced = functools.partial(_forced, "JB_LLOYD_WIDE")
+gmm_wide_forced = functools.partial(_forced, "JB_GMM_WIDE")
 
 
 def signature(row_ptr, fidx, fval, n: int, hash_num: int, seed: int, mode: int, bits, norms) -> None:

@@ -140,6 +140,24 @@ def test_lloyd_wide_range_and_shape_checks():
         call(10, 3, 5, nw=9)
 
 
+# (n, d, k) -> bytes of the Lloyd and of the GMM EM workspace: 4 (fixed + G partial) with G = min(slabs,
+# 256, room), Lloyd fixed 4 + k and partial k d + k, GMM fixed k d + 2 k and partial 2 k d + k. The 256 MiB
+# cap on the workspace (room) binds in the two rows at n 100000; the last two are outside the range.
+WORK_BYTES = [(1, 1, 1, 28, 24), (65, 1, 3, 76, 108), (17000, 3, 5, 20516, 35940), (777, 33, 130, 442536, 889200),
+              (2100, 8, 1024, 4870160, 9232384),
+              (100000, 2048, 1024, 260177936, 260116480),   # G 31 and 15
+              (100000, 4096, 1024, 251723792, 251695104),   # G 15 and 7
+              (4, 2, 1025, 0, 0), (2, 4097, 1024, 0, 0)]
+
+
+@pytest.mark.parametrize("n,d,k,lloyd,gmm", WORK_BYTES)
+def test_wide_workspace_sizes(n, d, k, lloyd, gmm):
+    """the geometry the two whole-GPU chains share (csrc/hip/jb_slab.hpp), through their work-size entries"""
+    from jubatus_amd.ops import hip
+    assert int(hip._fn("jb_lloyd_wide_work")(n, d, k)) == lloyd
+    assert int(hip._fn("jb_gmm_em_wide_work")(n, d, k)) == gmm
+
+
 @pytest.mark.parametrize("keys", [600, 1100])   # k x dims 4800: lloyd_kernel's; 8800: past its LDS, the wide chain
 def test_clustering_driver_runs_lloyd_on_the_device(keys):
     """k 8 over `keys` numeric keys, method kmeans: the device engine runs a

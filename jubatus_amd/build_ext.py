@@ -87,7 +87,8 @@ def build_native(force: bool = False, nproc: int = 8) -> str:
 # (jb_slab.hpp, the layer the two files share, is included from them only)
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_FILE_FLAGS = {"gmm_wide.hip": _NO_PK_F32,
-                  "kmeans_wide.hip": _NO_PK_F32}   # its sums must keep one fixed fp32 order, as gmm_wide's
+                  "kmeans_wide.hip": _NO_PK_F32,   # its sums must keep one fixed fp32 order, as gmm_wide's
+                  "kmeanspp_wide.hip": _NO_PK_F32}   # (includes jb_slab.hpp; an fmaf chain in column order)
 
 
 def build_hip(force: bool = False, nproc: int = 8) -> str:

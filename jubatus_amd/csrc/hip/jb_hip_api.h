@@ -88,6 +88,24 @@ int jb_lloyd_wide(const float* X, int n, int d, const float* w, float* C, int k,
                   float atol, float rtol, int32_t* assign, int32_t* done_iters, void* work,
                   int64_t work_bytes, hipStream_t stream);
 
+// kmeanspp_wide.hip
+// k-means++ seeding on the whole GPU with jb_kmeanspp's draw rule, for
+// 1 <= m <= n < 2^31, 1 <= d < 2^31: one launch per draw and a tail launch, no
+// host synchronisation. out [m], status [1]: as jb_kmeanspp (status j + 1 and
+// out[j] = -1 when draw j found zero mass; out past j is then not written).
+// nearest [n] (may be null): for every row the index into out of its nearest
+// chosen row, the first on ties. jb_kmeanspp_wide_work: the device workspace
+// in bytes, 0 outside the range (jb_kmeanspp_wide returns -2 there); its last
+// 4 n bytes are d2 [n], every row's squared distance to its nearest chosen
+// row. jb_kmeanspp_wide_pays: 1 when the shape is in range, jb_kmeanspp's
+// LDS-resident kernels do not take it and n * d reaches the measured
+// threshold: the one routing rule of every caller.
+int64_t jb_kmeanspp_wide_work(int n, int d, int m);
+int jb_kmeanspp_wide(const float* X, int n, int d, const float* w, const double* u, int m,
+                     int32_t* out, int32_t* status, int32_t* nearest, void* work,
+                     int64_t work_bytes, hipStream_t stream);
+int jb_kmeanspp_wide_pays(int n, int d, int m);
+
 // hot.hip
 int jb_hot_detect(const int64_t* row_ptr, int n, const int32_t* fidx, int64_t max_slots,
                   int block_min, int min_count, int max_rows, int32_t* gkey, int32_t* gcnt,

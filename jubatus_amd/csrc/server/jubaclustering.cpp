@@ -586,14 +586,36 @@ class Clustering : public HostEngine {
     h2d(dx, X.data(), 4 * n * D);
     h2d(dw, w.data(), 4 * n);
     h2d(du, u.data(), 8 * (size_t)m);
-    if (jb_kmeanspp(dx, (int)n, (int)D, dw, du, (int)m, scr, scr + n, dout, dout + m, st_) != 0)
+    // the whole-GPU chain where it pays (JB_KMEANSPP_WIDE=1: wherever it is in
+    // range, for A/B runs), as models/clustering.py _kmeanspp; it also leaves
+    // every row's nearest chosen row, which compress() takes
+    static const bool wide_forced = [] {
+      const char* e = getenv("JB_KMEANSPP_WIDE");
+      return e != nullptr && e[0] == '1';
+    }();
+    const bool in_i32 = n <= (size_t)INT32_MAX && D <= (size_t)INT32_MAX;
+    const int64_t wb = in_i32 && (wide_forced || jb_kmeanspp_wide_pays((int)n, (int)D, (int)m))
+                           ? jb_kmeanspp_wide_work((int)n, (int)D, (int)m)
+                           : 0;
+    kpp_nearest_.clear();
+    if (wb) {
+      if (jb_kmeanspp_wide(dx, (int)n, (int)D, dw, du, (int)m, dout, dout + m, dA_.get(n), dWork_.get((size_t)wb), wb,
+                           st_) != 0)
+        throw std::runtime_error("jb_kmeanspp_wide failed");
+    } else if (jb_kmeanspp(dx, (int)n, (int)D, dw, du, (int)m, scr, scr + n, dout, dout + m, st_) != 0) {
       throw std::runtime_error("jb_kmeanspp failed");
+    }
     std::vector<int32_t> o((size_t)m + 1);
     d2h(o.data(), dout, 4 * ((size_t)m + 1));
     sync();
     const int status = o[(size_t)m];
     std::vector<int64_t> chosen;
     if (status == 0) {
+      if (wb) {
+        kpp_nearest_.resize(n);
+        d2h(kpp_nearest_.data(), dA_.get(n), 4 * n);
+        sync();
+      }
       for (int64_t j = 0; j < m; ++j) chosen.push_back(o[(size_t)j]);
       return chosen;
     }
@@ -655,7 +677,7 @@ class Clustering : public HostEngine {
     for (int64_t r : reps) C.insert(C.end(), X.begin() + r * (int64_t)D, X.begin() + (r + 1) * (int64_t)D);
     // (X is in dX_ from the k-means++ call: its kernel path uploaded it, and
     // its host fallback's sqdist calls upload the same rows)
-    const auto asg = nearest(X, n, C, reps.size(), D, true);
+    const auto asg = kpp_nearest_.size() == n ? kpp_nearest_ : nearest(X, n, C, reps.size(), D, true);
     if (prof_.on) prof_.us[8] += since_us(t0);
     std::vector<float> ws(reps.size(), 0.f);
     for (size_t i = 0; i < n; ++i) ws[(size_t)asg[i]] += w[i];
@@ -1068,7 +1090,9 @@ class Clustering : public HostEngine {
   Dev<float> dX_, dW_, dC_, dXn_, dCn_, dOut_, dScr_, dV_, dP_;
   Dev<double> dU_;
   Dev<int32_t> dI_, dA_;
-  Dev<uint8_t> dWork_;              // jb_lloyd_wide's, then jb_gmm_em_wide's workspace
+  Dev<uint8_t> dWork_;              // jb_kmeanspp_wide's, jb_lloyd_wide's, then jb_gmm_em_wide's workspace
+  // the last kmeanspp(): every row's nearest chosen row when the chain ran to the end
+  std::vector<int32_t> kpp_nearest_;
 
   // Copies through page-locked staging: from pageable memory the runtime
   // stages each copy through a buffer of its own and waits for it (27 such

@@ -268,6 +268,8 @@ class Clustering:
             self.n_clusters = 0     # dbscan: clusters and noise points of the last run
             self.n_noise = 0
             self._rng = random.Random(self.seed)
+            self._kpp_wide_runs = 0     # seedings that ran the whole-GPU chain (hip.kmeanspp_wide)
+            self._kpp_nearest = None
 
     # ------------------------------------------------------------ tensors
     def _t(self):
@@ -384,11 +386,21 @@ class Clustering:
         n = X.shape[0]
         m = min(m, n)
         chosen: list[int] = []
+        self._kpp_nearest = None          # the chain's nearest-representative table of this call, for _compress
         if X.is_cuda:
             from ..ops import hip
             # one uniform per draw, as the host path's random.choices uses
-            chosen, status = hip.kmeanspp(X.contiguous(), w.contiguous(),
-                                          [rng.random() for _ in range(m)], m)
+            Xc, wc, u = X.contiguous(), w.contiguous(), [rng.random() for _ in range(m)]
+            wide = None
+            if hip.kmeanspp_wide_forced() or hip.kmeanspp_wide_pays(n, X.shape[1], m):
+                wide = hip.kmeanspp_wide(Xc, wc, u, m)     # (None: outside the chain's range)
+            if wide is not None:
+                chosen, status, nearest, _ = wide
+                self._kpp_wide_runs += 1
+                if status == 0:
+                    self._kpp_nearest = nearest
+            else:
+                chosen, status = hip.kmeanspp(Xc, wc, u, m)
             if status == 0:
                 return chosen
             chosen = chosen[:status - 1]      # zero mass left: finish on the host
@@ -422,7 +434,10 @@ class Clustering:
         X = self._dense_keys(ps, keys)
         w = torch.tensor(ps.w, dtype=torch.float32, device=X.device)
         reps = self._kmeanspp(X, w, m, self._rng)
-        a = self._sqdist(X, X[reps]).argmin(1)
+        if self._kpp_nearest is not None:   # the seeding chain relaxed every row against every representative
+            a = self._kpp_nearest.long()
+        else:
+            a = self._sqdist(X, X[reps]).argmin(1)
         wsum = torch.zeros(len(reps), dtype=torch.float32, device=X.device).index_add_(0, a, w)
         ws = wsum.cpu().numpy().astype(np.float64)
         keep = [j for j in range(len(reps)) if ws[j] > 0]

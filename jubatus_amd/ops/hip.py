@@ -161,6 +161,10 @@ _SIGS = {
     "jb_fvw_name_bytes": (_i64, []),
     "jb_kmeanspp": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
                            _c_void_p, _c_void_p, _c_void_p]),
+    "jb_kmeanspp_wide_work": (_i64, [_i32, _i32, _i32]),
+    "jb_kmeanspp_wide": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
+                                _c_void_p, _c_void_p, _i64, _c_void_p]),
+    "jb_kmeanspp_wide_pays": (_i32, [_i32, _i32, _i32]),
     "jb_gmm_em": (_i32, [_c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
                          _i32, _c_void_p, _c_void_p]),
     "jb_gmm_em_wide_work": (_i64, [_i32, _i32, _i32]),
@@ -340,6 +344,40 @@ def kmeanspp(X: torch.Tensor, w: torch.Tensor, u, m: int):
     return o[:m], o[m]
 
 
+def kmeanspp_wide(X: torch.Tensor, w: torch.Tensor, u, m: int):
+    """kmeanspp on the whole GPU (csrc/hip/kmeanspp_wide.hip: one launch per
+    draw, every workgroup a contiguous range of rows) for 1 <= m <= n: same
+    operands and draw rule -> (rows list, status, nearest, d2), or None outside
+    that range. nearest: device int32 [n], the index into rows of every row's
+    nearest chosen row (the first on ties); d2: device float32 [n], its squared
+    distance. Both describe rows[:status - 1] only when status != 0."""
+    import numpy as np
+    _dev(X, torch.float32, "X")
+    _dev(w, torch.float32, "w")
+    n, d = X.shape
+    if w.numel() < n or len(u) < m:
+        raise ValueError("kmeanspp_wide: bad operand shapes")
+    dev = X.device
+    work = _wide_work("jb_kmeanspp_wide_work", n, d, m, dev)
+    if work is None:
+        return None
+    ud = torch.from_numpy(np.asarray(u[:m], dtype=np.float64)).to(dev)
+    out = torch.empty(m + 1, dtype=torch.int32, device=dev)
+    nearest = torch.empty(n, dtype=torch.int32, device=dev)
+    rc = _fn("jb_kmeanspp_wide")(_p(X), n, d, _p(w), _p(ud), m, _p(out), out.data_ptr() + 4 * m, _p(nearest),
+                                 _p(work), work.numel(), _stream())
+    _check(rc, "jb_kmeanspp_wide")
+    o = out.cpu().tolist()
+    return o[:m], o[m], nearest, work[work.numel() - 4 * n:].view(torch.float32)
+
+
+def kmeanspp_wide_pays(n: int, d: int, m: int) -> bool:
+    """the routing rule of kmeanspp's callers: the chain is in range, the
+    LDS-resident kernels do not take the shape, and n * d reaches the measured
+    threshold (csrc/hip/kmeanspp_wide.hip kPaysFloats)"""
+    return max(n, d, m) < 2**31 and bool(_fn("jb_kmeanspp_wide_pays")(n, d, m))
+
+
 def lloyd(X: torch.Tensor, w: torch.Tensor, C: torch.Tensor, iters: int, atol: float,
           rtol: float):
     """weighted Lloyd iterations on one workgroup until allclose(C', C) or
@@ -449,6 +487,7 @@ def _forced(name: str) -> bool:
 
 lloyd_wide_forced = functools.partial(_forced, "JB_LLOYD_WIDE")
 gmm_wide_forced = functools.partial(_forced, "JB_GMM_WIDE")
+kmeanspp_wide_forced = functools.partial(_forced, "JB_KMEANSPP_WIDE")
 
 
 def signature(row_ptr, fidx, fval, n: int, hash_num: int, seed: int, mode: int, bits, norms) -> None:

@@ -336,10 +336,10 @@ int jb_topk_direct_query_path(const uint64_t* qbits, const float* qnorm, int nq,
                               float* scratch_d, int32_t* scratch_i, float* out_d_host,
                               int32_t* out_i_host, uint32_t* done_host, int path,
                               hipStream_t stream);
-void jb_topk_set_prof(long long* prof);
+int jb_topk_default_path(int mode, int64_t nrows, int k, int nq);
 int jb_topk_scores_direct_path(const float* src_d, int flip, int nq, int64_t nrows, int k,
                                float* scratch_d, int32_t* scratch_i, float* out_d_host,
-                               int32_t* out_i_host, uint32_t* done_host, int path_sel,
+                               int32_t* out_i_host, uint32_t* done_host, int path,
                                hipStream_t stream);
 int jb_topk_scores_direct(const float* src_d, int flip, int nq, int64_t nrows, int k,
                           float* scratch_d, int32_t* scratch_i, float* out_d_host,

@@ -22,6 +22,37 @@
 // Ties are broken by the lower row index (the CPU oracle's stable order).
 // Distances: metric 0 lsh (hamming / hash_num), 2 minhash (mismatch
 // fraction), 1 euclid_lsh (law of cosines on the norms). Invalid rows: +inf.
+//
+// K1 + K2 are the tile path. jb_topk (results in device memory) always takes
+// it; the latency entry points (results in pinned host memory, waited for:
+// jb_topk_direct_query for signatures, jb_topk_scores_direct for score
+// vectors) choose among five exact paths in default_path(), which also holds
+// the measurements behind every threshold:
+//
+//   path            serves by default                 kernels
+//   0 tile          signatures and scores under       topk_kernel, or for several signature
+//                   16384 rows; signatures, k <= 16,  queries topk_wq_kernel, or from 2M rows and
+//                   up to 2M rows (but see 4); the    k <= 32 topk_mq_sample_kernel +
+//                   rerun of a run that flagged a     topk_mq_kernel; then
+//                   retry                             topk_merge_sorted_kernel (k <= 16) or
+//                                                     topk_kernel<2> (the merge)
+//   1 radix chain   scores, several queries           radix_hist_kernel / radix_select_kernel
+//                                                     (two levels), topk_collect_kernel,
+//                                                     topk_rank_final_kernel
+//   2 grid barrier  signatures, k > 16,               topk_fused_kernel (one launch)
+//                   rows x k > 2^26, under 2M rows
+//   4 LDS select    scores, one query; signatures,    topk_select_kernel (one launch)
+//                   k > 16 up to rows x k = 2^26, or
+//                   several queries with k <= 16 on
+//                   up to 262144 rows
+//   - sampled       signatures from 2M rows           topk_sample_kernel, topk_collect_kernel,
+//                                                     topk_final_kernel
+//
+// The numbers are the `path` argument of the *_path entry points, which tests
+// and the A/B tools use to reach a kernel at shapes the default would not
+// pick (the sampled path cannot be forced). Paths 1, 2 and the sampled path
+// flag a retry when their candidate buffer overflows or comes up short; the
+// host then reruns the tile path.
 #include <limits.h>
 
 #include <atomic>
@@ -997,97 +1028,6 @@ __global__ __launch_bounds__(kMqT) void topk_mq_kernel(const TopkSrc s, int nq, 
   }
 }
 
-// Small k (<= KL): every thread keeps its own sorted top-KL of the items it
-// reads (strided across the block's range) in registers and the block merges
-// once at the end (per-wave pops, then wave 0). Used for the final merge of
-// the blocks' candidates (a few items per thread); on a long scan with random
-// distances the per-thread insertions cost more than the tile kernel's
-// threshold-pruned selection (measured, tools/bench_topk.py).
-template <int MODE, int KL, int NW = 4>
-__global__ __launch_bounds__(NW * 64) void topk_lists_kernel(const TopkSrc s, int64_t n,
-                                                             int64_t per_block, int k,
-                                                             float* __restrict__ out_d,
-                                                             int32_t* __restrict__ out_i,
-                                                             volatile uint32_t* done = nullptr,
-                                                             uint32_t seq = 0) {
-  constexpr int T = NW * 64;
-  __shared__ float s_wd[NW * KL];
-  __shared__ int s_wi[NW * KL];
-  __shared__ float s_cd[KL];
-  __shared__ int s_ci[KL];
-  __shared__ uint64_t s_q[kTopMaxWords];
-  const int q = blockIdx.y;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  float qn = 0.f;
-  if (MODE == 0) {
-    for (int w = t; w < s.words; w += T) s_q[w] = s.qbits[(int64_t)q * s.words + w];
-    qn = s.qnorm[q];
-  }
-  __syncthreads();
-  uint64_t qb[kTopMaxWords];
-#pragma unroll
-  for (int w = 0; w < kTopMaxWords; ++w) qb[w] = (MODE == 0 && w < s.words) ? s_q[w] : 0ull;
-  float ld[KL];
-  int li[KL];
-#pragma unroll
-  for (int j = 0; j < KL; ++j) { ld[j] = INFINITY; li[j] = INT_MAX; }
-  const int64_t b0 = (int64_t)blockIdx.x * per_block;
-  const int64_t b1 = b0 + per_block < n ? b0 + per_block : n;
-  for (int64_t base = b0; base < b1; base += (int64_t)T * 4) {
-    float d[4];
-    int ix[4];
-    {   // 4 rows in flight per thread
-      int64_t rows[4], nn[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        rows[r] = base + (int64_t)r * T + t;
-        nn[r] = rows[r] < b1 ? n : 0;
-      }
-      load_rows<MODE, 4>(s, q, nn, rows, qb, qn, d, ix);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float v = d[r];
-      const int id = ix[r];
-      if (lt_pair(v, id, ld[KL - 1], li[KL - 1])) {
-#pragma unroll
-        for (int j = KL - 1; j > 0; --j) {
-          const bool up = lt_pair(v, id, ld[j - 1], li[j - 1]);
-          const bool here = !up && lt_pair(v, id, ld[j], li[j]);
-          ld[j] = up ? ld[j - 1] : (here ? v : ld[j]);
-          li[j] = up ? li[j - 1] : (here ? id : li[j]);
-        }
-        if (lt_pair(v, id, ld[0], li[0])) { ld[0] = v; li[0] = id; }
-      }
-    }
-  }
-  wave_pop<KL>(ld, li, k, &s_wd[wv * k], &s_wi[wv * k], lane);
-  __syncthreads();
-  if (wv == 0) {
-    constexpr int M = (NW * KL + 63) / 64;
-    float m[M];
-    int mi[M];
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-      const int c = lane + 64 * j;
-      if (c < NW * k) { m[j] = s_wd[c]; mi[j] = s_wi[c]; }
-      else { m[j] = INFINITY; mi[j] = INT_MAX; }
-    }
-    __builtin_amdgcn_wave_barrier();
-    sort_regs<M>(m, mi);
-    wave_pop<M>(m, mi, k, s_cd, s_ci, lane);
-  }
-  __syncthreads();
-  const int64_t o = ((int64_t)q * gridDim.x + blockIdx.x) * k;
-  if (done != nullptr) {   // pinned host memory, then the flag (sys_store)
-    for (int j = t; j < k; j += T) { sys_store(out_d + o + j, s_cd[j]); sys_store(out_i + o + j, s_ci[j]); }
-    sys_stores_block_done();
-    if (t == 0) sys_store(const_cast<uint32_t*>(done) + q, seq);
-    return;
-  }
-  for (int j = t; j < k; j += T) { out_d[o + j] = s_cd[j]; out_i[o + j] = s_ci[j]; }
-}
-
 // ---------------------------------------------------------------------------
 // Sampled-threshold top-k (latency path, large tables): O(N) with a small
 // constant for any k <= 128, instead of the tile kernel's O(N k / tile).
@@ -1096,7 +1036,7 @@ __global__ __launch_bounds__(NW * 64) void topk_lists_kernel(const TopkSrc s, in
 //       ~3k rows of the full table are expected at or below T);
 //   S2  full scan: rows with d <= T are appended to a candidate buffer
 //       (wave-aggregated atomics: one atomic per wave per pass);
-//   S3  exact top-k of the candidates (topk_lists / topk_kernel), written to
+//   S3  exact top-k of the candidates (topk_final_kernel), written to
 //       pinned host memory; done[q] = seq, or seq | kTopRetry when T was too
 //       low (fewer than k candidates) or the buffer overflowed - the host
 //       then reruns the exact tile path.
@@ -1293,7 +1233,10 @@ __global__ __launch_bounds__(1024) void topk_final_kernel(const float* __restric
   if (t == 0) sys_store(const_cast<uint32_t*>(done) + q, retry ? (seq | kTopRetry) : seq);
 }
 
-constexpr int kListK = 16;   // k up to this uses topk_lists_kernel
+// k up to this: the final merge of the blocks' lists is one wave's
+// (topk_merge_sorted_kernel), and the sampled and grid-barrier finals select
+// from per-thread register lists instead of ranking the candidates in LDS
+constexpr int kListK = 16;
 
 // Waves per block of the scan stage (MODE 0/1). Every block scans a
 // contiguous range with a block-wide carry and two barriers per tile, so a
@@ -1309,10 +1252,6 @@ inline int scan_waves(int k, int nq, int64_t nrows) {
   // queries: 182 vs 55 us); equal at 1M rows x 1 query
   return nq == 1 && nrows >= ((int64_t)2 << 20) ? 16 : 4;
 }
-
-// the final merge of the blocks' candidates for k <= kListK uses per-thread
-// register lists (measured ~3 us faster than the tile kernel's rank merge,
-// profiles/r02_lsh_merge_ab.jsonl)
 
 // JB_TOPK_MQ=0 turns the register multi-query scan off (A/B runs)
 // JB_TOPK_MQ_MIN_ROWS: the table size from which the multi-query scan runs
@@ -1461,9 +1400,9 @@ inline int launch_scan(const TopkSrc& s, int blocks, int nq, int64_t nrows, int6
 // k <= kListK and <= kMergeLists blocks: ONE wave per query. The lists go to
 // LDS; lane l owns lists l, l + 64, ... and keeps their heads in registers;
 // each of k rounds takes the wave's arg-min head (DPP / permlane) and its
-// owner advances that list. The per-thread insertion lists of
-// topk_lists_kernel cost ~20 us here (16 waves of VALU pops on a handful of
-// real candidates); this is k rounds of a dozen register steps.
+// owner advances that list. Per-thread insertion lists (a kernel since
+// retired) cost ~20 us here (16 waves of VALU pops on a handful of real
+// candidates); this is k rounds of a dozen register steps.
 constexpr int kMergeLists = 512;
 constexpr int kMergeStageT = 256;   // threads staging the lists into LDS (wave 0 merges)
 __global__ __launch_bounds__(kMergeStageT) void topk_merge_sorted_kernel(const float* __restrict__ cd,
@@ -1545,272 +1484,97 @@ __global__ __launch_bounds__(kMergeStageT) void topk_merge_sorted_kernel(const f
   for (int j = lane; j < k; j += 64) { out_d[o + j] = s_rd[j]; out_i[o + j] = s_ri[j]; }
 }
 
-// the final merge: one block per query; 16 waves when the (17 k) candidates
-// of the merge stage fit (k <= 37), else 4
-inline void launch_merge(const TopkSrc& m, int nq, int64_t nc, int k, float* out_d,
-                         int32_t* out_i, volatile uint32_t* done, uint32_t seq,
-                         hipStream_t stream) {
-  if (k <= kListK && nc % k == 0 && nc / k <= kMergeLists) {
+// Where a launch leaves its [nq][k] results: device memory (done == nullptr),
+// or fine-grained pinned host memory followed by done[q] = seq per query (the
+// latency paths; a kernel may publish seq | kTopRetry instead).
+struct TopkOut {
+  float* out_d;
+  int32_t* out_i;
+  volatile uint32_t* done;
+  uint32_t seq;
+};
+
+// the most blocks a query's tile scan runs (tile_grid()); with kMqBlocksMax
+// the most lists a scan hands to the merge
+constexpr int kTileBlocksMax = 256;
+static_assert(kMqBlocksMax + 1 <= kMergeLists, "the multi-query scan's lists exceed the one-wave merge");
+static_assert(kTileBlocksMax <= kMergeLists, "the tile scan's lists exceed the one-wave merge");
+
+// the final merge of `lists` sorted lists of k candidates per query (m.src_d /
+// m.src_i): one block per query; past kListK 16 waves when the (17 k)
+// candidates of the merge stage fit (k <= 37), else 4. -2: more lists than
+// the one-wave merge holds (no scan produces that many, see above).
+inline int launch_merge(const TopkSrc& m, int nq, int lists, int k, const TopkOut& o, hipStream_t stream) {
+  const int64_t nc = (int64_t)lists * k;   // candidates per query
+  if (k <= kListK) {
+    if (lists > kMergeLists) return -2;
     hipLaunchKernelGGL(topk_merge_sorted_kernel, dim3(nq), dim3(kMergeStageT), (size_t)nc * 8, stream, m.src_d, m.src_i,
-                       (int)(nc / k), k, out_d, out_i, done, seq);
-  } else if (k <= kListK) {
-    hipLaunchKernelGGL((topk_lists_kernel<2, kListK, 16>), dim3(1, nq), dim3(16 * 64), 0, stream,
-                       m, nc, nc, k, out_d, out_i, done, seq);
+                       lists, k, o.out_d, o.out_i, o.done, o.seq);
   } else if (k <= 37) {
     const int64_t tile = 16 * 64 * kTopR;
     hipLaunchKernelGGL((topk_kernel<2, 16>), dim3(1, nq), dim3(16 * 64), 0, stream, m, nc,
-                       ((nc + tile - 1) / tile) * tile, k, out_d, out_i, done, seq);
+                       ((nc + tile - 1) / tile) * tile, k, o.out_d, o.out_i, o.done, o.seq);
   } else {
     hipLaunchKernelGGL((topk_kernel<2, 4>), dim3(1, nq), dim3(4 * 64), 0, stream, m, nc,
-                       ((nc + kTopTile - 1) / kTopTile) * kTopTile, k, out_d, out_i, done, seq);
+                       ((nc + kTopTile - 1) / kTopTile) * kTopTile, k, o.out_d, o.out_i, o.done, o.seq);
   }
+  return 0;
 }
 
 }  // namespace jb
 
-// Top-k smallest distances of nq queries.
-//   mode 0: fused signature scan (qbits [nq][words], tbits [nrows][words],
-//           norms, valid, metric 0 lsh / 1 euclid_lsh / 2 minhash)
-//   mode 1: score vector src_d [nq][nrows] (flip: distance = 1 - score)
-// out_d / out_i: [nq][k] (+inf / INT_MAX padding). scratch_d / scratch_i:
-// >= nq * jb_topk_blocks(nrows, k) * k entries each. k <= 128.
-static int topk_tile_blocks(int64_t nrows, int k) {
-  if (k <= 0 || nrows <= 0) return 0;
-  const int64_t tiles = (nrows + jb::kTopTile - 1) / jb::kTopTile;
-  // bound the candidates K2 merges; one block per CU is enough to stream
-  // the table (the scan is a few bytes per row)
-  // (256: more blocks measured slower for batched queries,
-  // profiles/r02_lsh_block_cap.jsonl; again with the one-wave merge: 512
-  // blocks took one query at 1M rows 44 -> 42 us but four 48 -> 65 us and one
-  // at 10M rows 102 -> 121 us, profiles/r4_topk_lsh_blocks512.jsonl)
-  constexpr int64_t cap = 256;
-  int64_t max_blocks = 8192 / k < cap ? 8192 / k : cap;
-  if (max_blocks < 1) max_blocks = 1;
-  const int64_t tiles_per_block = (tiles + max_blocks - 1) / max_blocks;
-  return (int)((tiles + tiles_per_block - 1) / tiles_per_block);
-}
-
-// candidate lists the scratch must hold per query: the tile kernels' grid,
-// or the multi-query scan's (up to jb::kMqBlocksMax blocks on tables of
-// kMqMinRows and more: two blocks a CU keep more rows in flight than one)
-extern "C" int jb_topk_blocks(int64_t nrows, int k) {
-  const int tb = topk_tile_blocks(nrows, k);
-  if (tb > 0 && nrows >= jb::mq_min_rows() && k <= jb::kMqMaxK)
-    return tb > jb::kMqBlocksMax + 1 ? tb : jb::kMqBlocksMax + 1;
-  return tb;
-}
-
-extern "C" int jb_topk(int mode, const uint64_t* qbits, const float* qnorm, int nq,
-                       const uint64_t* tbits, const float* tnorm, const uint8_t* valid,
-                       int64_t nrows, int words, int hash_num, int metric, const float* src_d,
-                       int flip, int k, float* scratch_d, int32_t* scratch_i, float* out_d,
-                       int32_t* out_i, hipStream_t stream) {
-  if (nq <= 0 || nrows <= 0 || k <= 0) return 0;
-  if (k > jb::kTopMaxK || words > jb::kTopMaxWords || (mode != 0 && mode != 1)) return -2;
-  const int blocks = topk_tile_blocks(nrows, k);
-  const int lists = jb_topk_blocks(nrows, k);
-  const int64_t tiles = (nrows + jb::kTopTile - 1) / jb::kTopTile;
-  const int64_t per_block = ((tiles + blocks - 1) / blocks) * jb::kTopTile;
-  jb::TopkSrc s{qbits, qnorm, tbits, tnorm, valid, words, hash_num, metric, src_d, nullptr, flip};
-  const int used = mode == 0 ? jb::launch_scan<0>(s, blocks, nq, nrows, per_block, k, scratch_d, scratch_i, stream,
-                                                  lists)
-                              : jb::launch_scan<1>(s, blocks, nq, nrows, per_block, k, scratch_d, scratch_i, stream,
-                                                  lists);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  const int64_t nc = (int64_t)used * k;   // candidates per query
-  jb::TopkSrc m{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, scratch_d, scratch_i, 0};
-  jb::launch_merge(m, nq, nc, k, out_d, out_i, nullptr, 0u, stream);
-  return (int)hipGetLastError();
-}
-
-// Latency path (mode 0): as jb_topk, but the final merge writes straight into
-// fine-grained pinned host memory and publishes done[q] = seq per query
-// (tile path).
-static int topk_to_host_tile(const uint64_t* qbits, const float* qnorm, int nq,
-                             const uint64_t* tbits, const float* tnorm, const uint8_t* valid,
-                             int64_t nrows, int words, int hash_num, int metric, int k,
-                             float* scratch_d, int32_t* scratch_i, float* out_d_host,
-                             int32_t* out_i_host, uint32_t* done_host, uint32_t seq,
-                             hipStream_t stream) {
-  const int blocks = topk_tile_blocks(nrows, k);
-  const int64_t tiles = (nrows + jb::kTopTile - 1) / jb::kTopTile;
-  const int64_t per_block = ((tiles + blocks - 1) / blocks) * jb::kTopTile;
-  jb::TopkSrc s{qbits, qnorm, tbits, tnorm, valid, words, hash_num, metric, nullptr, nullptr, 0};
-  const int used = jb::launch_scan<0>(s, blocks, nq, nrows, per_block, k, scratch_d, scratch_i, stream,
-                                      jb_topk_blocks(nrows, k));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  const int64_t nc = (int64_t)used * k;
-  jb::TopkSrc m{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, scratch_d, scratch_i, 0};
-  jb::launch_merge(m, nq, nc, k, out_d_host, out_i_host, (volatile uint32_t*)done_host, seq,
-                   stream);
-  return (int)hipGetLastError();
-}
-
-// scratch layout of the sampled path (in scratch_d / scratch_i, sized by
-// jb_topk_direct_scratch): thr[8] | count[8] | candidates [nq][kCandCap]
+// Scratch layout of the latency paths, in entries of scratch_d / scratch_i
+// (each jb_topk_direct_scratch entries, or the tile path's nq x
+// jb_topk_blocks x k block lists from entry 0 if that is more):
+//   [0, 8)     thr (scratch_d) / count (scratch_i), one per query
+//   [16, 32)   sel (scratch_i): the radix chain's bucket words, 2 x 8
+//   [64, ...)  candidates [nq][kCandCap]; the radix chain's two histogram
+//              levels [nq][kRadixBins] follow its nq queries' candidates and
+//              are cleared by every run
+//   [kFuseStateOff, + kFuseStateWords)  state that is zero between launches
+//              (jb_topk_scratch_init once, then every kernel leaves it zero):
+//              h1 [8][kRadixBins] | h2 [8][kRadixBins] | sync [8][kSyncWords],
+//              after the candidates of 8 queries and out of reach of the tile
+//              path's block lists (<= 8 x 256 x 128 entries)
 constexpr int kCandCap = 65536;
 constexpr int64_t kSampleMax = 16384;
-
-// j for the sampled threshold, 0 when the tile path is the better choice
-// (below ~2M rows the tile path is as fast, and it cannot overflow on rows
-// that tie at the threshold - e.g. duplicated data)
-static int sample_j(int64_t nrows, int k) {
-  if (nrows < (int64_t)2 << 20) return 0;
-  const int64_t S = nrows < kSampleMax ? nrows : kSampleMax;
-  const double j = 4.0 * k * (double)S / (double)nrows;
-  const int jj = (int)j + 3;
-  return jj <= 16 ? jj : 0;
-}
-
-// + the radix-select histograms of the score path: 2 levels x nq x 4096
 constexpr int kRadixBins = 4096;
-// the one-launch score top-k keeps per-query histograms and counters that
-// must be zero when it starts (it leaves them zero when it ends): a fixed
-// region after the candidates of 8 queries, out of reach of the tile path's
-// block candidates (<= 8 x 256 x 128 entries)
-constexpr int64_t kFuseStateOff = 64 + 8 * (int64_t)kCandCap;
-constexpr int64_t kFuseStateWords = 2 * 8 * (int64_t)kRadixBins + 8 * 4;
+// per query: arrivals, candidates and finished blocks of the grid-barrier
+// launch, finished blocks of the LDS-select launch
+constexpr int kSyncWords = 4;
+constexpr int64_t kCandOff = 64;
+constexpr int64_t kFuseStateOff = kCandOff + 8 * (int64_t)kCandCap;
+constexpr int64_t kFuseStateWords = 2 * 8 * (int64_t)kRadixBins + 8 * kSyncWords;
+
+struct TopkScratch {
+  float* d;
+  int32_t* i;
+  float* thr() const { return d; }
+  int* count() const { return i; }
+  uint32_t* sel() const { return (uint32_t*)i + 16; }
+  float* cand_d() const { return d + kCandOff; }
+  int32_t* cand_i() const { return i + kCandOff; }
+  uint32_t* chain_hist(int nq) const { return (uint32_t*)(i + kCandOff + (int64_t)nq * kCandCap); }
+  uint32_t* state() const { return (uint32_t*)(i + kFuseStateOff); }
+  uint32_t* fuse_h1() const { return state(); }
+  uint32_t* fuse_h2() const { return state() + 8 * kRadixBins; }
+  uint32_t* fuse_sync() const { return state() + 16 * kRadixBins; }
+  // query 0's finished-block counter of the LDS-select launch (query q's is kSyncWords x q on)
+  uint32_t* select_counter() const { return fuse_sync() + 3; }
+};
+
 extern "C" int64_t jb_topk_direct_scratch(int nq) {
   (void)nq;
   return kFuseStateOff + kFuseStateWords;
 }
 
-// zero the score top-k's state region of a scratch allocation (once, after
-// allocating it; scratch_i as passed to jb_topk_scores_direct)
+// zero the state region of a scratch allocation (once, after allocating it;
+// scratch_i as passed to the latency entry points)
 extern "C" int jb_topk_scratch_init(int32_t* scratch_i, hipStream_t stream) {
   hipError_t e = hipMemsetAsync(scratch_i + kFuseStateOff, 0, sizeof(int32_t) * kFuseStateWords,
                                 stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);   // done before any stream uses it
   return (int)e;
-}
-
-template <int MODE>
-static int topk_fused_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k,
-                             float* scratch_d, int32_t* scratch_i, float* out_d_host,
-                             int32_t* out_i_host, uint32_t* done_host, uint32_t seq,
-                             hipStream_t stream);
-
-template <int MODE>
-static int topk_onepass_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k, float* scratch_d,
-                               int32_t* scratch_i, float* out_d_host, int32_t* out_i_host,
-                               uint32_t* done_host, uint32_t seq, hipStream_t stream);
-
-template <int MODE>
-static int topk_select_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k, float* scratch_d,
-                              int32_t* scratch_i, float* out_d_host, int32_t* out_i_host,
-                              uint32_t* done_host, uint32_t seq, hipStream_t stream);
-
-// the LDS-select launch by default (tools/bench_topk_lsh.py, 100 K and 1M
-// rows): for k past kListK while rows x k stays moderate (1M rows: k 31 67 us
-// vs 80, 4 queries k 40 81 vs 131; k 100 106 vs 91 one launch), and for
-// several queries on small tables (100 K rows, 4 x k 10: 38 vs 44 us; at 1M
-// the tile path's multi-query scan wins, 49 vs 92)
-static bool select_default(int64_t nrows, int k, int nq) {
-  if (nrows < 16384) return false;
-  if (k > jb::kListK) return nrows * k <= ((int64_t)64 << 20);
-  return nq > 1 && nrows <= 256 * 1024;
-}
-
-// path: -1 default, 0 tile, 2 one launch (grid barriers), 3 one pass, 4 LDS select. Default (measured at 1M rows,
-// profiles/r03_topk_paths_ab.jsonl): the tile path up to k = kListK (k 10:
-// 58 us vs 86 us one launch, whose two grid barriers cost more than the
-// tile path's second launch), one launch past it (k 100: 94 us vs 224 us,
-// the tile path's per-tile selection grows with k); the sampled path from 2M
-// rows
-static int topk_to_host_any(const uint64_t* qbits, const float* qnorm, int nq,
-                            const uint64_t* tbits, const float* tnorm, const uint8_t* valid,
-                            int64_t nrows, int words, int hash_num, int metric, int k,
-                            float* scratch_d, int32_t* scratch_i, float* out_d_host,
-                            int32_t* out_i_host, uint32_t* done_host, uint32_t seq,
-                            hipStream_t stream, int path = -1) {
-  const int j = sample_j(nrows, k);
-  if (path == 3) {
-    jb::TopkSrc s{qbits, qnorm, tbits, tnorm, valid, words, hash_num, metric, nullptr, nullptr, 0};
-    return topk_onepass_launch<0>(s, nq, nrows, k, scratch_d, scratch_i, out_d_host, out_i_host,
-                                  done_host, seq, stream);
-  }
-  if (path == 4 || (path < 0 && j == 0 && select_default(nrows, k, nq))) {
-    jb::TopkSrc s{qbits, qnorm, tbits, tnorm, valid, words, hash_num, metric, nullptr, nullptr, 0};
-    return topk_select_launch<0>(s, nq, nrows, k, scratch_d, scratch_i, out_d_host, out_i_host, done_host,
-                                 seq, stream);
-  }
-  if (path == 2 || (path < 0 && j == 0 && nrows >= 16384 && k > jb::kListK)) {
-    jb::TopkSrc s{qbits, qnorm, tbits, tnorm, valid, words, hash_num, metric, nullptr, nullptr, 0};
-    return topk_fused_launch<0>(s, nq, nrows, k, scratch_d, scratch_i, out_d_host, out_i_host,
-                                done_host, seq, stream);
-  }
-  if (j == 0 || path == 0)
-    return topk_to_host_tile(qbits, qnorm, nq, tbits, tnorm, valid, nrows, words, hash_num,
-                             metric, k, scratch_d, scratch_i, out_d_host, out_i_host, done_host,
-                             seq, stream);
-  jb::TopkSrc s{qbits, qnorm, tbits, tnorm, valid, words, hash_num, metric, nullptr, nullptr, 0};
-  float* thr = scratch_d;                         // [8]
-  int* count = scratch_i;                         // [8]
-  float* cand_d = scratch_d + 64;
-  int32_t* cand_i = scratch_i + 64;
-  const int64_t S = nrows < kSampleMax ? nrows : kSampleMax;
-  hipLaunchKernelGGL(jb::topk_sample_kernel<0>, dim3(nq), dim3(jb::kSampleThreads), 0, stream, s,
-                     nrows, S, j, thr, count);
-  int64_t cblocks = (nrows + 1023) / 1024;        // 4 rows per thread
-  if (cblocks > 1024) cblocks = 1024;
-  hipLaunchKernelGGL(jb::topk_collect_kernel<0>, dim3((unsigned)cblocks, nq), dim3(256), 0, stream,
-                     s, nrows, thr, kCandCap, cand_d, cand_i, count);
-  hipLaunchKernelGGL(jb::topk_final_kernel, dim3(nq), dim3(1024), 0, stream, cand_d, cand_i,
-                     count, kCandCap, k, thr, out_d_host, out_i_host,
-                     (volatile uint32_t*)done_host, seq);
-  return (int)hipGetLastError();
-}
-
-// launch + wait; a sampled run whose threshold missed reruns the tile path
-static int topk_direct_run(const uint64_t* qbits, const float* qnorm, int nq,
-                           const uint64_t* tbits, const float* tnorm, const uint8_t* valid,
-                           int64_t nrows, int words, int hash_num, int metric, int k,
-                           float* scratch_d, int32_t* scratch_i, float* out_d_host,
-                           int32_t* out_i_host, uint32_t* done_host, hipStream_t stream,
-                           int path = -1) {
-  uint32_t seq = jb::next_seq();
-  int rc = topk_to_host_any(qbits, qnorm, nq, tbits, tnorm, valid, nrows, words, hash_num, metric,
-                            k, scratch_d, scratch_i, out_d_host, out_i_host, done_host, seq,
-                            stream, path);
-  if (rc != 0) return rc;
-  bool retry = false;
-  rc = jb::wait_flags_status(done_host, nq, seq, jb::kTopRetry, stream, &retry);
-  if (rc != 0 || !retry) return rc;
-  seq = jb::next_seq();
-  rc = topk_to_host_tile(qbits, qnorm, nq, tbits, tnorm, valid, nrows, words, hash_num, metric, k,
-                         scratch_d, scratch_i, out_d_host, out_i_host, done_host, seq, stream);
-  if (rc != 0) return rc;
-  return jb::wait_flags(done_host, nq, seq, stream);
-}
-
-// query signatures on the device -> top-k in pinned host memory, waited for
-extern "C" int jb_topk_direct_query(const uint64_t* qbits, const float* qnorm, int nq,
-                                    const uint64_t* tbits, const float* tnorm,
-                                    const uint8_t* valid, int64_t nrows, int words, int hash_num,
-                                    int metric, int k, float* scratch_d, int32_t* scratch_i,
-                                    float* out_d_host, int32_t* out_i_host, uint32_t* done_host,
-                                    hipStream_t stream) {
-  if (nq <= 0 || nrows <= 0 || k <= 0) return 0;
-  if (k > jb::kTopMaxK || words > jb::kTopMaxWords || nq > 8) return -2;
-  return topk_direct_run(qbits, qnorm, nq, tbits, tnorm, valid, nrows, words, hash_num, metric, k,
-                         scratch_d, scratch_i, out_d_host, out_i_host, done_host, stream);
-}
-
-// as jb_topk_direct_query with the path forced (A/B in tools/bench_topk_lsh.py):
-// -1 default, 0 tile, 2 one launch
-extern "C" int jb_topk_direct_query_path(const uint64_t* qbits, const float* qnorm, int nq,
-                                         const uint64_t* tbits, const float* tnorm,
-                                         const uint8_t* valid, int64_t nrows, int words,
-                                         int hash_num, int metric, int k, float* scratch_d,
-                                         int32_t* scratch_i, float* out_d_host,
-                                         int32_t* out_i_host, uint32_t* done_host, int path,
-                                         hipStream_t stream) {
-  if (nq <= 0 || nrows <= 0 || k <= 0) return 0;
-  if (k > jb::kTopMaxK || words > jb::kTopMaxWords || nq > 8) return -2;
-  return topk_direct_run(qbits, qnorm, nq, tbits, tnorm, valid, nrows, words, hash_num, metric, k,
-                         scratch_d, scratch_i, out_d_host, out_i_host, done_host, stream, path);
 }
 
 // Score-vector latency path (mode 1: [nq][nrows] similarity / distance from
@@ -1823,7 +1587,7 @@ extern "C" int jb_topk_direct_query_path(const uint64_t* qbits, const float* qno
 //   R4  the sub-bucket holding the k-th smallest -> threshold T (all rows
 //       with key <= T: at most k + that sub-bucket's size);
 //   R5  collect the rows <= T (topk_collect_kernel), R6 exact top-k of the
-//       candidates into pinned host memory (topk_final_kernel).
+//       candidates into pinned host memory (topk_rank_final_kernel).
 // Cost: three 4-byte reads per row, no per-tile sorting, independent of k.
 // Ties beyond the candidate buffer (e.g. thousands of identical distances)
 // flag a retry and the exact tile path reruns.
@@ -2034,13 +1798,14 @@ __global__ __launch_bounds__(1024) void topk_rank_final_kernel(
 namespace jb {
 
 // ---------------------------------------------------------------------------
-// Exact top-k as ONE launch, for a score vector (MODE 1: the inverted-index
-// scan's output) or straight off the signature table (MODE 0: lsh /
-// minhash / euclid_lsh distances computed in place). Replaces chains of
-// dependent launches (score path: hist / select / hist / select / collect /
-// final plus a histogram memset; signature path: per-block tile top-k, then
-// a merge of blocks x k candidates) whose gaps and serial merges dominated a
-// ~1M-row query. A grid of B blocks per query, at most as many blocks as are
+// Exact top-k as ONE launch straight off the signature table (lsh / minhash /
+// euclid_lsh distances computed in place). Replaces the tile path's two
+// dependent launches (per-block tile top-k, then a merge of blocks x k
+// candidates), whose per-tile selection grows with k. (On score vectors the
+// same kernel lost to the radix chain on every measured shape - 80-86 us
+// against 48-61 us at 1M rows, 6x slower on heavy ties,
+// profiles/r03_topk_paths_ab.jsonl - and that instantiation was retired.)
+// A grid of B blocks per query, at most as many blocks as are
 // co-resident (kFuseThreads threads, 48 KB of LDS each), every block owning a
 // contiguous range of rows:
 //   A  distances of its rows (kept in LDS for the first kFuseCache rows),
@@ -2059,7 +1824,7 @@ namespace jb {
 // Ties are broken by the lower row index (lt_pair), like the tile path.
 constexpr int kFuseThreads = 256;
 constexpr int kFuseMaxBlocks = 256;
-constexpr int kFuseSync = 4;            // per query: arrivals, candidates, finished, pad
+constexpr int kFuseSync = kSyncWords;   // the query's sync words (scratch layout above)
 constexpr int kFuseCache = 8192;        // distances kept in LDS per block
 
 __device__ __forceinline__ uint32_t ld_agent_u32(const uint32_t* p) {
@@ -2119,17 +1884,15 @@ __device__ __forceinline__ void fused_bin(uint32_t* h, bool act, uint32_t bin, i
   else if (act && bin != b0) atomicAdd(&h[bin], 1u);
 }
 
-// the distance of row r (MODE as load_item; r < n)
-template <int MODE>
+// the signature distance of row r (r < n)
 __device__ __forceinline__ float fused_dist(const TopkSrc& s, int q, int64_t n, int64_t r,
                                             const uint64_t* qb, float qn) {
   float d;
   int id;
-  load_item<MODE>(s, q, n, r, qb, qn, d, id);
+  load_item<0>(s, q, n, r, qb, qn, d, id);
   return d;
 }
 
-template <int MODE>
 __global__ __launch_bounds__(kFuseThreads) void topk_fused_kernel(
     const TopkSrc s, int64_t n, int k, uint32_t* __restrict__ h1, uint32_t* __restrict__ h2,
     uint32_t* __restrict__ sync, float* __restrict__ cand_d, int32_t* __restrict__ cand_i,
@@ -2145,15 +1908,12 @@ __global__ __launch_bounds__(kFuseThreads) void topk_fused_kernel(
   const int q = blockIdx.y;
   const int t = threadIdx.x, lane = t & 63;
   const uint32_t B = gridDim.x;
-  float qn = 0.f;
-  if (MODE == 0) {
-    for (int w = t; w < s.words; w += kFuseThreads) s_q[w] = s.qbits[(int64_t)q * s.words + w];
-    qn = s.qnorm[q];
-  }
+  for (int w = t; w < s.words; w += kFuseThreads) s_q[w] = s.qbits[(int64_t)q * s.words + w];
+  const float qn = s.qnorm[q];
   __syncthreads();
   uint64_t qb[kTopMaxWords];
 #pragma unroll
-  for (int w = 0; w < kTopMaxWords; ++w) qb[w] = (MODE == 0 && w < s.words) ? s_q[w] : 0ull;
+  for (int w = 0; w < kTopMaxWords; ++w) qb[w] = w < s.words ? s_q[w] : 0ull;
   uint32_t* g1 = h1 + (int64_t)q * kRadixBins;
   uint32_t* g2 = h2 + (int64_t)q * kRadixBins;
   uint32_t* qs = sync + (int64_t)q * kFuseSync;
@@ -2169,7 +1929,7 @@ __global__ __launch_bounds__(kFuseThreads) void topk_fused_kernel(
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int64_t r = b + u * kFuseThreads;
-      d[u] = fused_dist<MODE>(s, q, n, r < end ? r : end - 1, qb, qn);
+      d[u] = fused_dist(s, q, n, r < end ? r : end - 1, qb, qn);
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -2184,7 +1944,7 @@ __global__ __launch_bounds__(kFuseThreads) void topk_fused_kernel(
   fused_barrier(qs, B);
   // the distance of row r in passes B and C: LDS for the cached rows
   auto dist_of = [&](int64_t r) -> float {
-    return r < cend ? s_cache[r - beg] : fused_dist<MODE>(s, q, n, r, qb, qn);
+    return r < cend ? s_cache[r - beg] : fused_dist(s, q, n, r, qb, qn);
   };
   // B
   fused_select(g1, (uint32_t)k, h, sel);               // h doubles as the scan buffer
@@ -2307,162 +2067,8 @@ __global__ __launch_bounds__(kFuseThreads) void topk_fused_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// One pass, one launch, no grid barrier (k <= kListK): B blocks of 256
-// threads each stream a contiguous range of rows, 8 rows per thread in flight
-// (every load of a round issued before the first use). A thread keeps its
-// sorted top-KL (distance, row) pairs in registers and inserts only below its
-// current KL-th, so after the first rounds a row costs a compare. The block
-// pops its k best (wave pops, then wave 0) into global candidates (write-
-// through stores, no fence) and counts itself finished; the last block of
-// the query merges the B x k
-// candidates the same way, writes the k results into pinned host memory,
-// resets the counter and publishes done[q]. Every block's range is read once
-// from HBM; the only serialization is the one counter per block.
-constexpr int kOnepassRows = 8;
-
-template <int MODE>
-__global__ __launch_bounds__(256) void topk_onepass_kernel(const TopkSrc s, int64_t n, int64_t per_block,
-                                                           int k, float* __restrict__ cand_d,
-                                                           int32_t* __restrict__ cand_i, int cap,
-                                                           uint32_t* __restrict__ counter,
-                                                           float* __restrict__ out_d,
-                                                           int32_t* __restrict__ out_i,
-                                                           volatile uint32_t* done, uint32_t seq,
-                                                           long long* __restrict__ prof) {
-  constexpr int NW = 4, T = NW * 64, KL = kListK, R = kOnepassRows;
-  // diagnostics (prof != nullptr): realtime stamps (100 MHz) per block:
-  // start, rows done, block pop done, published; the last block adds merge
-  // loads done, final pop done, end
-  auto stamp = [&](int i) {
-    if (prof != nullptr && threadIdx.x == 0)
-      prof[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + i] = (long long)__builtin_amdgcn_s_memrealtime();
-  };
-  stamp(0);
-  __shared__ float s_wd[NW * KL];
-  __shared__ int s_wi[NW * KL];
-  __shared__ float s_cd[KL];
-  __shared__ int s_ci[KL];
-  __shared__ uint64_t s_q[kTopMaxWords];
-  __shared__ int s_last;
-  const int q = blockIdx.y;
-  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  float qn = 0.f;
-  if (MODE == 0) {
-    for (int w = t; w < s.words; w += T) s_q[w] = s.qbits[(int64_t)q * s.words + w];
-    qn = s.qnorm[q];
-  }
-  __syncthreads();
-  uint64_t qb[kTopMaxWords];
-#pragma unroll
-  for (int w = 0; w < kTopMaxWords; ++w) qb[w] = (MODE == 0 && w < s.words) ? s_q[w] : 0ull;
-  float ld[KL];
-  int li[KL];
-#pragma unroll
-  for (int j = 0; j < KL; ++j) { ld[j] = INFINITY; li[j] = INT_MAX; }
-  auto insert = [&](float v, int id) {
-    if (lt_pair(v, id, ld[KL - 1], li[KL - 1])) {
-#pragma unroll
-      for (int j = KL - 1; j > 0; --j) {
-        const bool up = lt_pair(v, id, ld[j - 1], li[j - 1]);
-        const bool here = !up && lt_pair(v, id, ld[j], li[j]);
-        ld[j] = up ? ld[j - 1] : (here ? v : ld[j]);
-        li[j] = up ? li[j - 1] : (here ? id : li[j]);
-      }
-      if (lt_pair(v, id, ld[0], li[0])) { ld[0] = v; li[0] = id; }
-    }
-  };
-  const int64_t b0 = (int64_t)blockIdx.x * per_block;
-  const int64_t b1 = b0 + per_block < n ? b0 + per_block : n;
-  for (int64_t base = b0; base < b1; base += (int64_t)T * R) {
-    float d[R];
-    int ix[R];
-    {
-      int64_t rows[R], nn[R];
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        rows[r] = base + (int64_t)r * T + t;
-        nn[r] = rows[r] < b1 ? n : 0;
-      }
-      load_rows<MODE, R>(s, q, nn, rows, qb, qn, d, ix);
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) insert(d[r], ix[r]);
-  }
-  stamp(1);
-  // the block's k best (wave pops, then wave 0) -> s_cd / s_ci
-  auto block_pop = [&]() {
-    wave_pop<KL>(ld, li, k, &s_wd[wv * k], &s_wi[wv * k], lane);
-    __syncthreads();
-    if (wv == 0) {
-      constexpr int M = (NW * KL + 63) / 64;
-      float m[M];
-      int mi[M];
-#pragma unroll
-      for (int j = 0; j < M; ++j) {
-        const int c = lane + 64 * j;
-        m[j] = c < NW * k ? s_wd[c] : INFINITY;
-        mi[j] = c < NW * k ? s_wi[c] : INT_MAX;
-      }
-      __builtin_amdgcn_wave_barrier();
-      sort_regs<M>(m, mi);
-      wave_pop<M>(m, mi, k, s_cd, s_ci, lane);
-    }
-    __syncthreads();
-  };
-  block_pop();
-  stamp(2);
-  // publish the candidates [q][block][k] cross-XCD without a fence
-  // (MI355X_MICROARCH.md, visibility): write-through (sc1) stores, every
-  // storing wave drains them, a barrier, then ONE agent-scope add whose
-  // returned value tells the last block; that block reads them with sc1 loads
-  float* cd = cand_d + (int64_t)q * cap;
-  int32_t* ci = cand_i + (int64_t)q * cap;
-  if (t < k) {
-    __hip_atomic_store(cd + (int64_t)blockIdx.x * k + t, s_cd[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(ci + (int64_t)blockIdx.x * k + t, s_ci[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  uint32_t* qc = counter + (int64_t)q * kFuseSync;     // the query's counter word
-  if (t == 0)
-    s_last = __hip_atomic_fetch_add(qc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
-  __syncthreads();
-  stamp(3);
-  if (!s_last) return;
-  // the last block: merge the B x k candidates, 8 pairs in flight per
-  // thread (a load -> insert loop would wait one L2 round trip per pair)
-#pragma unroll
-  for (int j = 0; j < KL; ++j) { ld[j] = INFINITY; li[j] = INT_MAX; }
-  const int nc = (int)gridDim.x * k;
-  for (int j0 = t; j0 < nc; j0 += 8 * T) {
-    float v[8];
-    int vi[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int j = j0 + u * T < nc ? j0 + u * T : nc - 1;
-      v[u] = __hip_atomic_load(cd + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      vi[u] = __hip_atomic_load(ci + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (j0 + u * T < nc) insert(v[u], vi[u]);
-  }
-  stamp(4);
-  block_pop();
-  stamp(5);
-  float* od = out_d + (int64_t)q * k;
-  int32_t* oi = out_i + (int64_t)q * k;
-  if (t < k) { od[t] = s_cd[t]; oi[t] = s_ci[t]; }
-  if (t == 0) __hip_atomic_store(qc, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // next launch
-  __threadfence_system();
-  __syncthreads();
-  if (t == 0) done[q] = seq;
-  stamp(6);
-}
-
-// ---------------------------------------------------------------------------
 // Tables up to ~1M rows, k up to kTopMaxK, one launch without a grid barrier
-// (the one-launch kernel above waits twice for every block): B blocks per
+// (the grid-barrier kernel above waits twice for every block): B blocks per
 // query stream contiguous ranges in chunks of kSelChunk rows. The rows of a
 // chunk that beat the block's running k-th (all of them until it has k) are
 // appended to LDS after the running top-k, in row order, and an exact select
@@ -2760,129 +2366,105 @@ __global__ __launch_bounds__(kSelThreads) void topk_select_kernel(
 
 }  // namespace jb
 
-// blocks of one fused launch that are resident at once (all queries): the
-// grid barrier needs every block running; bounded by kFuseMaxBlocks
-static int fused_resident_blocks() {
-  static int cached = 0;
-  if (cached == 0) {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, jb::topk_fused_kernel<1>,
-                                                     jb::kFuseThreads, 0) != hipSuccess) {
-      cus = 64;
-      per_cu = 1;
-    }
-    int64_t r = (int64_t)cus * (per_cu > 0 ? per_cu : 1);
-    cached = (int)(r < jb::kFuseMaxBlocks ? r : jb::kFuseMaxBlocks);
-  }
-  return cached;
+// ---------------------------------------------------------------------------
+// Host side: one launch helper per path, the choice among them, the entry
+// points.
+
+// The tile path's grid: blocks per query and rows per block (whole tiles).
+struct TileGrid {
+  int blocks;
+  int64_t per_block;
+};
+static TileGrid tile_grid(int64_t nrows, int k) {
+  if (k <= 0 || nrows <= 0) return {0, 0};
+  const int64_t tiles = (nrows + jb::kTopTile - 1) / jb::kTopTile;
+  // bound the candidates K2 merges; one block per CU is enough to stream
+  // the table (the scan is a few bytes per row)
+  // (kTileBlocksMax 256: more blocks measured slower for batched queries,
+  // profiles/r02_lsh_block_cap.jsonl; again with the one-wave merge: 512
+  // blocks took one query at 1M rows 44 -> 42 us but four 48 -> 65 us and one
+  // at 10M rows 102 -> 121 us, profiles/r4_topk_lsh_blocks512.jsonl)
+  int64_t max_blocks = 8192 / k < jb::kTileBlocksMax ? 8192 / k : jb::kTileBlocksMax;
+  if (max_blocks < 1) max_blocks = 1;
+  const int64_t tiles_per_block = (tiles + max_blocks - 1) / max_blocks;
+  const int blocks = (int)((tiles + tiles_per_block - 1) / tiles_per_block);
+  return {blocks, ((tiles + blocks - 1) / blocks) * jb::kTopTile};
 }
 
+// candidate lists the scratch must hold per query: the tile kernels' grid,
+// or the multi-query scan's (up to jb::kMqBlocksMax blocks on tables of
+// kMqMinRows and more: two blocks a CU keep more rows in flight than one)
+extern "C" int jb_topk_blocks(int64_t nrows, int k) {
+  const int tb = tile_grid(nrows, k).blocks;
+  if (tb > 0 && nrows >= jb::mq_min_rows() && k <= jb::kMqMaxK)
+    return tb > jb::kMqBlocksMax + 1 ? tb : jb::kMqBlocksMax + 1;
+  return tb;
+}
+
+// Path 0, tile: the scan (K1) into per-block lists at the start of the
+// scratch, then the merge (K2) into o.
 template <int MODE>
-static int topk_fused_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k,
-                             float* scratch_d, int32_t* scratch_i, float* out_d_host,
-                             int32_t* out_i_host, uint32_t* done_host, uint32_t seq,
-                             hipStream_t stream) {
-  uint32_t* st = (uint32_t*)(scratch_i + kFuseStateOff);
-  static const int64_t rows_per_block = [] {
-    const char* e = getenv("JB_FUSE_ROWS");                // diagnostics: rows per block
-    const long v = e != nullptr ? atol(e) : 0;
-    return (int64_t)(v >= 256 ? v : 1024);
-  }();
-  int64_t B = (nrows + rows_per_block - 1) / rows_per_block;
-  const int64_t bmax = fused_resident_blocks() / nq;
-  if (B > bmax) B = bmax;
-  if (B < 1) B = 1;
-  hipLaunchKernelGGL(jb::topk_fused_kernel<MODE>, dim3((unsigned)B, nq), dim3(jb::kFuseThreads), 0,
-                     stream, s, nrows, k, st, st + 8 * kRadixBins, st + 16 * kRadixBins,
-                     scratch_d + 64, scratch_i + 64, kCandCap, out_d_host, out_i_host,
-                     (volatile uint32_t*)done_host, seq);
+static int tile_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k, const TopkScratch& sc,
+                       const jb::TopkOut& o, hipStream_t stream) {
+  const TileGrid g = tile_grid(nrows, k);
+  const int used = jb::launch_scan<MODE>(s, g.blocks, nq, nrows, g.per_block, k, sc.d, sc.i, stream,
+                                         jb_topk_blocks(nrows, k));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  const jb::TopkSrc m{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, sc.d, sc.i, 0};
+  const int rc = jb::launch_merge(m, nq, used, k, o, stream);
+  return rc != 0 ? rc : (int)hipGetLastError();
+}
+
+// Top-k smallest distances of nq queries.
+//   mode 0: fused signature scan (qbits [nq][words], tbits [nrows][words],
+//           norms, valid, metric 0 lsh / 1 euclid_lsh / 2 minhash)
+//   mode 1: score vector src_d [nq][nrows] (flip: distance = 1 - score)
+// out_d / out_i: [nq][k] (+inf / INT_MAX padding). scratch_d / scratch_i:
+// >= nq * jb_topk_blocks(nrows, k) * k entries each. k <= 128.
+extern "C" int jb_topk(int mode, const uint64_t* qbits, const float* qnorm, int nq,
+                       const uint64_t* tbits, const float* tnorm, const uint8_t* valid,
+                       int64_t nrows, int words, int hash_num, int metric, const float* src_d,
+                       int flip, int k, float* scratch_d, int32_t* scratch_i, float* out_d,
+                       int32_t* out_i, hipStream_t stream) {
+  if (nq <= 0 || nrows <= 0 || k <= 0) return 0;
+  if (k > jb::kTopMaxK || words > jb::kTopMaxWords || (mode != 0 && mode != 1)) return -2;
+  const jb::TopkSrc s{qbits, qnorm, tbits, tnorm, valid, words, hash_num, metric, src_d, nullptr, flip};
+  const TopkScratch sc{scratch_d, scratch_i};
+  const jb::TopkOut o{out_d, out_i, nullptr, 0u};
+  return mode == 0 ? tile_launch<0>(s, nq, nrows, k, sc, o, stream) : tile_launch<1>(s, nq, nrows, k, sc, o, stream);
+}
+
+// The latency paths below write into pinned host memory and publish
+// o.done[q] = o.seq per query.
+
+// j of the sampled threshold: about 4 x k rows of the table are expected at
+// or below the sample's j-th smallest distance. From kSampledMinRows rows and
+// k <= 128 it is at most 7, within topk_sample_kernel's 16-entry lists.
+static int sampled_j(int64_t nrows, int k) {
+  const int64_t S = nrows < kSampleMax ? nrows : kSampleMax;
+  return (int)(4.0 * k * (double)S / (double)nrows) + 3;
+}
+
+// Sampled path (signatures): threshold from a sample, collect, final.
+static int sampled_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k, const TopkScratch& sc,
+                          const jb::TopkOut& o, hipStream_t stream) {
+  const int64_t S = nrows < kSampleMax ? nrows : kSampleMax;
+  hipLaunchKernelGGL(jb::topk_sample_kernel<0>, dim3(nq), dim3(jb::kSampleThreads), 0, stream, s,
+                     nrows, S, sampled_j(nrows, k), sc.thr(), sc.count());
+  int64_t cblocks = (nrows + 1023) / 1024;        // 4 rows per thread
+  if (cblocks > 1024) cblocks = 1024;
+  hipLaunchKernelGGL(jb::topk_collect_kernel<0>, dim3((unsigned)cblocks, nq), dim3(256), 0, stream,
+                     s, nrows, sc.thr(), kCandCap, sc.cand_d(), sc.cand_i(), sc.count());
+  hipLaunchKernelGGL(jb::topk_final_kernel, dim3(nq), dim3(1024), 0, stream, sc.cand_d(), sc.cand_i(),
+                     sc.count(), kCandCap, k, sc.thr(), o.out_d, o.out_i, o.done, o.seq);
   return (int)hipGetLastError();
 }
 
-// diagnostics: phase stamps of the one-pass kernel (tools/bench_topk_phases.py)
-static long long* g_topk_prof = nullptr;
-extern "C" void jb_topk_set_prof(long long* prof) { g_topk_prof = prof; }
-
-// one-pass launch (k <= kListK): blocks of 2048 rows (one round of 8 rows a
-// thread) up to 512 blocks; the counter is word 3 of the query's sync words
-// in the zeroed state region (the fused kernel leaves it zero too)
-template <int MODE>
-static int topk_onepass_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k, float* scratch_d,
-                               int32_t* scratch_i, float* out_d_host, int32_t* out_i_host,
-                               uint32_t* done_host, uint32_t seq, hipStream_t stream) {
-  if (k > jb::kListK) return -2;
-  uint32_t* counter = (uint32_t*)(scratch_i + kFuseStateOff) + 16 * kRadixBins + 3;
-  constexpr int64_t rows_per_round = 256 * jb::kOnepassRows;
-  int64_t B = (nrows + rows_per_round - 1) / rows_per_round;
-  if (B > 512) B = 512;
-  const int64_t rounds = (nrows + B * rows_per_round - 1) / (B * rows_per_round);
-  const int64_t per_block = rounds * rows_per_round;
-  B = (nrows + per_block - 1) / per_block;
-  hipLaunchKernelGGL(jb::topk_onepass_kernel<MODE>, dim3((unsigned)B, nq), dim3(256), 0, stream, s, nrows,
-                     per_block, k, scratch_d + 64, scratch_i + 64, kCandCap, counter, out_d_host,
-                     out_i_host, (volatile uint32_t*)done_host, seq, g_topk_prof);
-  return (int)hipGetLastError();
-}
-
-// one-launch select path (k <= kTopMaxK): ~2048 rows a block, B x k
-// candidates at most kSelChunk (the last block's LDS); counter as the one-pass
-// launch's (each leaves it zero)
-template <int MODE>
-static int topk_select_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k, float* scratch_d,
-                              int32_t* scratch_i, float* out_d_host, int32_t* out_i_host,
-                              uint32_t* done_host, uint32_t seq, hipStream_t stream) {
-  if (k > jb::kTopMaxK || nq > 8) return -2;
-  uint32_t* counter = (uint32_t*)(scratch_i + kFuseStateOff) + 16 * kRadixBins + 3;
-  int64_t B = (nrows + 2047) / 2048;
-  const int64_t bmax = jb::kSelChunk / k;
-  if (B > bmax) B = bmax;
-  if (B > 256) B = 256;
-  if (B < 1) B = 1;
-  const int64_t per_block = (nrows + B - 1) / B;
-  B = (nrows + per_block - 1) / per_block;
-  hipLaunchKernelGGL(jb::topk_select_kernel<MODE>, dim3((unsigned)B, nq), dim3(jb::kSelThreads), 0, stream, s,
-                     nrows, per_block, k, scratch_d + 64, scratch_i + 64, kCandCap, counter, out_d_host,
-                     out_i_host, (volatile uint32_t*)done_host, seq);
-  return (int)hipGetLastError();
-}
-
-// path: 0 tile scan + merge, 1 radix chain (6 launches + memset), 2 one launch
-// (grid barriers), 3 one pass (k <= kListK), 4 one launch, LDS select
-static int topk_scores_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k, int path,
-                              float* scratch_d, int32_t* scratch_i, float* out_d_host,
-                              int32_t* out_i_host, uint32_t* done_host, uint32_t seq,
-                              hipStream_t stream) {
-  if (path == 2)
-    return topk_fused_launch<1>(s, nq, nrows, k, scratch_d, scratch_i, out_d_host, out_i_host,
-                                done_host, seq, stream);
-  if (path == 3)
-    return topk_onepass_launch<1>(s, nq, nrows, k, scratch_d, scratch_i, out_d_host, out_i_host,
-                                  done_host, seq, stream);
-  if (path == 4)
-    return topk_select_launch<1>(s, nq, nrows, k, scratch_d, scratch_i, out_d_host, out_i_host,
-                                 done_host, seq, stream);
-  if (path == 0) {
-    const int blocks = topk_tile_blocks(nrows, k);
-    const int64_t tiles = (nrows + jb::kTopTile - 1) / jb::kTopTile;
-    const int64_t per_block = ((tiles + blocks - 1) / blocks) * jb::kTopTile;
-    const int used = jb::launch_scan<1>(s, blocks, nq, nrows, per_block, k, scratch_d, scratch_i, stream,
-                                        jb_topk_blocks(nrows, k));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    const int64_t nc = (int64_t)used * k;
-    jb::TopkSrc m{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, scratch_d, scratch_i, 0};
-    jb::launch_merge(m, nq, nc, k, out_d_host, out_i_host, (volatile uint32_t*)done_host, seq,
-                     stream);
-    return (int)hipGetLastError();
-  }
-  float* thr = scratch_d;                          // [8]
-  int* count = scratch_i;                          // [8]
-  uint32_t* sel = (uint32_t*)scratch_i + 16;       // [2 x 8]
-  float* cand_d = scratch_d + 64;
-  int32_t* cand_i = scratch_i + 64;
-  uint32_t* h1 = (uint32_t*)(scratch_i + 64 + (int64_t)nq * kCandCap);
+// Path 1, radix chain (scores): 6 launches + a memset of the histograms.
+static int chain_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k, const TopkScratch& sc,
+                        const jb::TopkOut& o, hipStream_t stream) {
+  uint32_t* h1 = sc.chain_hist(nq);
   uint32_t* h2 = h1 + (int64_t)nq * kRadixBins;
   hipError_t e = hipMemsetAsync(h1, 0, sizeof(uint32_t) * 2 * (size_t)nq * kRadixBins, stream);
   if (e != hipSuccess) return (int)e;
@@ -2892,53 +2474,193 @@ static int topk_scores_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k
   constexpr int64_t hb_max = 512;
   int64_t hb = (nrows + 1023) / 1024;
   if (hb > hb_max) hb = hb_max;
-  const float* src = s.src_d;
-  hipLaunchKernelGGL(jb::radix_hist_kernel<1>, dim3((unsigned)hb, nq), dim3(256), 0, stream, src,
-                     s.flip, nrows, sel, h1);
-  hipLaunchKernelGGL(jb::radix_select_kernel<1>, dim3(nq), dim3(1024), 0, stream, h1, k, sel, thr,
-                     count);
-  hipLaunchKernelGGL(jb::radix_hist_kernel<2>, dim3((unsigned)hb, nq), dim3(256), 0, stream, src,
-                     s.flip, nrows, sel, h2);
-  hipLaunchKernelGGL(jb::radix_select_kernel<2>, dim3(nq), dim3(1024), 0, stream, h2, k, sel, thr,
-                     count);
+  hipLaunchKernelGGL(jb::radix_hist_kernel<1>, dim3((unsigned)hb, nq), dim3(256), 0, stream, s.src_d,
+                     s.flip, nrows, sc.sel(), h1);
+  hipLaunchKernelGGL(jb::radix_select_kernel<1>, dim3(nq), dim3(1024), 0, stream, h1, k, sc.sel(), sc.thr(),
+                     sc.count());
+  hipLaunchKernelGGL(jb::radix_hist_kernel<2>, dim3((unsigned)hb, nq), dim3(256), 0, stream, s.src_d,
+                     s.flip, nrows, sc.sel(), h2);
+  hipLaunchKernelGGL(jb::radix_select_kernel<2>, dim3(nq), dim3(1024), 0, stream, h2, k, sc.sel(), sc.thr(),
+                     sc.count());
   int64_t cblocks = (nrows + 1023) / 1024;
   if (cblocks > 1024) cblocks = 1024;
   hipLaunchKernelGGL(jb::topk_collect_kernel<1>, dim3((unsigned)cblocks, nq), dim3(256), 0, stream,
-                     s, nrows, thr, kCandCap, cand_d, cand_i, count);
-  hipLaunchKernelGGL(jb::topk_rank_final_kernel, dim3(nq), dim3(1024), 0, stream, cand_d, cand_i,
-                     count, kCandCap, k, thr, out_d_host, out_i_host,
-                     (volatile uint32_t*)done_host, seq);
+                     s, nrows, sc.thr(), kCandCap, sc.cand_d(), sc.cand_i(), sc.count());
+  hipLaunchKernelGGL(jb::topk_rank_final_kernel, dim3(nq), dim3(1024), 0, stream, sc.cand_d(), sc.cand_i(),
+                     sc.count(), kCandCap, k, sc.thr(), o.out_d, o.out_i, o.done, o.seq);
   return (int)hipGetLastError();
 }
 
-// path_sel: -1 default (the radix chain from 16384 rows), 0 tile, 1 radix
-// chain, 2 one launch (A/B in tools/bench_topk_scores.py: at 1M rows the
-// chain measured 48-61 us, the one launch 80-86 us, and 6x slower on heavy
-// ties at k = 100; profiles/r03_topk_paths_ab.jsonl)
+// blocks of one grid-barrier launch that are resident at once (all queries):
+// the barrier needs every block running; bounded by kFuseMaxBlocks
+static int fused_resident_blocks() {
+  static int cached = 0;
+  if (cached == 0) {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, jb::topk_fused_kernel, jb::kFuseThreads,
+                                                     0) != hipSuccess) {
+      cus = 64;
+      per_cu = 1;
+    }
+    int64_t r = (int64_t)cus * (per_cu > 0 ? per_cu : 1);
+    cached = (int)(r < jb::kFuseMaxBlocks ? r : jb::kFuseMaxBlocks);
+  }
+  return cached;
+}
+
+// Path 2, grid barriers (signatures): 1024 rows a block, as many blocks as
+// are resident at once.
+static int fused_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k, const TopkScratch& sc,
+                        const jb::TopkOut& o, hipStream_t stream) {
+  constexpr int64_t rows_per_block = 1024;
+  int64_t B = (nrows + rows_per_block - 1) / rows_per_block;
+  const int64_t bmax = fused_resident_blocks() / nq;
+  if (B > bmax) B = bmax;
+  if (B < 1) B = 1;
+  hipLaunchKernelGGL(jb::topk_fused_kernel, dim3((unsigned)B, nq), dim3(jb::kFuseThreads), 0, stream, s,
+                     nrows, k, sc.fuse_h1(), sc.fuse_h2(), sc.fuse_sync(), sc.cand_d(), sc.cand_i(), kCandCap,
+                     o.out_d, o.out_i, o.done, o.seq);
+  return (int)hipGetLastError();
+}
+
+// Path 4, LDS select (k <= kTopMaxK): ~2048 rows a block, B x k candidates at
+// most kSelChunk (the last block's LDS).
+template <int MODE>
+static int select_launch(const jb::TopkSrc& s, int nq, int64_t nrows, int k, const TopkScratch& sc,
+                         const jb::TopkOut& o, hipStream_t stream) {
+  int64_t B = (nrows + 2047) / 2048;
+  const int64_t bmax = jb::kSelChunk / k;
+  if (B > bmax) B = bmax;
+  if (B > 256) B = 256;
+  if (B < 1) B = 1;
+  const int64_t per_block = (nrows + B - 1) / B;
+  B = (nrows + per_block - 1) / per_block;
+  hipLaunchKernelGGL(jb::topk_select_kernel<MODE>, dim3((unsigned)B, nq), dim3(jb::kSelThreads), 0, stream, s,
+                     nrows, per_block, k, sc.cand_d(), sc.cand_i(), kCandCap, sc.select_counter(), o.out_d,
+                     o.out_i, o.done, o.seq);
+  return (int)hipGetLastError();
+}
+
+// The paths of the latency entry points; the values are the forced `path`
+// argument (kPathSampled cannot be forced: sampled_j() is sized for the
+// tables that take it by default).
+enum TopkPath { kPathTile = 0, kPathChain = 1, kPathFused = 2, kPathSelect = 4, kPathSampled = 5 };
+
+constexpr int64_t kSmallTable = 16384;                    // below: always the tile path
+constexpr int64_t kSampledMinRows = (int64_t)2 << 20;
+
+// The path a latency call takes when none is forced (mode as jb_topk's).
+static TopkPath default_path(int mode, int64_t nrows, int k, int nq) {
+  if (mode == 1) {
+    if (nrows < kSmallTable) return kPathTile;
+    // one query on the LDS select (tools/bench_topk_scores.py, 1M rows: k 10
+    // 44-56 us vs 47-101 on the radix chain, which degrades on quantized
+    // scores - k 100 with 64 score levels: 105 vs 631 us); several queries on
+    // the chain (4 x k 10: 55-66 vs 71-78 us without ties)
+    return nq == 1 ? kPathSelect : kPathChain;
+  }
+  // the sampled path from 2M rows: O(rows) with a small constant for any k;
+  // below that the tile path is as fast, and it cannot overflow on rows that
+  // tie at the threshold (e.g. duplicated data)
+  if (nrows >= kSampledMinRows) return kPathSampled;
+  if (nrows < kSmallTable) return kPathTile;
+  // Measured at 1M rows (profiles/r03_topk_paths_ab.jsonl): the tile path up
+  // to k = kListK (k 10: 58 us vs 86 us with grid barriers, whose two
+  // barriers cost more than the tile path's second launch), one launch past
+  // it (k 100: 94 us vs 224 us, the tile path's per-tile selection grows with
+  // k). Of the one-launch kernels (tools/bench_topk_lsh.py, 100 K and 1M
+  // rows) the LDS select wins while rows x k stays moderate (1M rows: k 31
+  // 67 us vs 80, 4 queries k 40 81 vs 131; k 100 106 vs 91 with grid
+  // barriers), and it takes several small-k queries on small tables (100 K
+  // rows, 4 x k 10: 38 vs 44 us on the tile path; at 1M the tile path's
+  // multi-query scan wins, 49 vs 92).
+  if (k > jb::kListK) return nrows * k <= ((int64_t)64 << 20) ? kPathSelect : kPathFused;
+  return nq > 1 && nrows <= 256 * 1024 ? kPathSelect : kPathTile;
+}
+
+// default_path() for tests and the A/B tools; -2: an argument out of range
+extern "C" int jb_topk_default_path(int mode, int64_t nrows, int k, int nq) {
+  if ((mode != 0 && mode != 1) || nrows <= 0 || k <= 0 || k > jb::kTopMaxK || nq <= 0 || nq > 8) return -2;
+  return default_path(mode, nrows, k, nq);
+}
+
+// -2: the mode has no such path
+static int path_launch(int mode, int path, const jb::TopkSrc& s, int nq, int64_t nrows, int k,
+                       const TopkScratch& sc, const jb::TopkOut& o, hipStream_t stream) {
+  switch (path) {
+    case kPathTile:
+      return mode == 0 ? tile_launch<0>(s, nq, nrows, k, sc, o, stream)
+                       : tile_launch<1>(s, nq, nrows, k, sc, o, stream);
+    case kPathSelect:
+      return mode == 0 ? select_launch<0>(s, nq, nrows, k, sc, o, stream)
+                       : select_launch<1>(s, nq, nrows, k, sc, o, stream);
+    case kPathChain: return mode == 1 ? chain_launch(s, nq, nrows, k, sc, o, stream) : -2;
+    case kPathFused: return mode == 0 ? fused_launch(s, nq, nrows, k, sc, o, stream) : -2;
+    case kPathSampled: return mode == 0 ? sampled_launch(s, nq, nrows, k, sc, o, stream) : -2;
+  }
+  return -2;
+}
+
+// launch + wait; a run that flags a retry (a threshold that missed, a
+// candidate buffer that overflowed) reruns on the tile path
+static int latency_run(int mode, int path, const jb::TopkSrc& s, int nq, int64_t nrows, int k,
+                       const TopkScratch& sc, float* out_d_host, int32_t* out_i_host, uint32_t* done_host,
+                       hipStream_t stream) {
+  jb::TopkOut o{out_d_host, out_i_host, done_host, jb::next_seq()};
+  int rc = path_launch(mode, path, s, nq, nrows, k, sc, o, stream);
+  if (rc != 0) return rc;
+  bool retry = false;
+  rc = jb::wait_flags_status(done_host, nq, o.seq, jb::kTopRetry, stream, &retry);
+  if (rc != 0 || !retry) return rc;
+  o.seq = jb::next_seq();
+  rc = path_launch(mode, kPathTile, s, nq, nrows, k, sc, o, stream);
+  if (rc != 0) return rc;
+  return jb::wait_flags(done_host, nq, o.seq, stream);
+}
+
+// Query signatures on the device -> top-k in pinned host memory, waited for.
+// path: -1 default_path(), or forced (tests, tools/bench_topk_lsh.py): 0 tile,
+// 2 grid barriers, 4 LDS select; -2 for any other.
+extern "C" int jb_topk_direct_query_path(const uint64_t* qbits, const float* qnorm, int nq,
+                                         const uint64_t* tbits, const float* tnorm,
+                                         const uint8_t* valid, int64_t nrows, int words,
+                                         int hash_num, int metric, int k, float* scratch_d,
+                                         int32_t* scratch_i, float* out_d_host,
+                                         int32_t* out_i_host, uint32_t* done_host, int path,
+                                         hipStream_t stream) {
+  if (nq <= 0 || nrows <= 0 || k <= 0) return 0;
+  if (k > jb::kTopMaxK || words > jb::kTopMaxWords || nq > 8 || path == kPathSampled) return -2;
+  const jb::TopkSrc s{qbits, qnorm, tbits, tnorm, valid, words, hash_num, metric, nullptr, nullptr, 0};
+  return latency_run(0, path < 0 ? default_path(0, nrows, k, nq) : path, s, nq, nrows, k,
+                     TopkScratch{scratch_d, scratch_i}, out_d_host, out_i_host, done_host, stream);
+}
+
+extern "C" int jb_topk_direct_query(const uint64_t* qbits, const float* qnorm, int nq,
+                                    const uint64_t* tbits, const float* tnorm,
+                                    const uint8_t* valid, int64_t nrows, int words, int hash_num,
+                                    int metric, int k, float* scratch_d, int32_t* scratch_i,
+                                    float* out_d_host, int32_t* out_i_host, uint32_t* done_host,
+                                    hipStream_t stream) {
+  return jb_topk_direct_query_path(qbits, qnorm, nq, tbits, tnorm, valid, nrows, words, hash_num, metric, k,
+                                   scratch_d, scratch_i, out_d_host, out_i_host, done_host, -1, stream);
+}
+
+// Score vectors [nq][nrows] on the device (flip: distance = 1 - score) ->
+// top-k in pinned host memory, waited for. path: -1 default_path(), or forced
+// (tests, tools/bench_topk_scores.py): 0 tile, 1 radix chain, 4 LDS select; -2
+// for any other. Tables under kSmallTable rows take the tile path whatever
+// path is given.
 extern "C" int jb_topk_scores_direct_path(const float* src_d, int flip, int nq, int64_t nrows,
                                           int k, float* scratch_d, int32_t* scratch_i,
                                           float* out_d_host, int32_t* out_i_host,
-                                          uint32_t* done_host, int path_sel, hipStream_t stream) {
+                                          uint32_t* done_host, int path, hipStream_t stream) {
   if (nq <= 0 || nrows <= 0 || k <= 0) return 0;
   if (k > jb::kTopMaxK || nq > 8) return -2;
-  jb::TopkSrc s{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, src_d, nullptr, flip};
-  // default: one query on the LDS select (tools/bench_topk_scores.py, 1M rows:
-  // k 10 44-56 us vs 47-101 on the radix chain, which degrades on quantized
-  // scores - k 100 with 64 score levels: 105 vs 631 us); several queries on
-  // the chain (4 x k 10: 55-66 vs 71-78 us without ties)
-  const int path = nrows >= 16384 ? (path_sel < 0 ? (nq == 1 ? 4 : 1) : path_sel) : 0;
-  uint32_t seq = jb::next_seq();
-  int rc = topk_scores_launch(s, nq, nrows, k, path, scratch_d, scratch_i, out_d_host,
-                              out_i_host, done_host, seq, stream);
-  if (rc != 0) return rc;
-  bool retry = false;
-  rc = jb::wait_flags_status(done_host, nq, seq, jb::kTopRetry, stream, &retry);
-  if (rc != 0 || !retry) return rc;
-  seq = jb::next_seq();
-  rc = topk_scores_launch(s, nq, nrows, k, 0, scratch_d, scratch_i, out_d_host, out_i_host,
-                          done_host, seq, stream);
-  if (rc != 0) return rc;
-  return jb::wait_flags(done_host, nq, seq, stream);
+  const jb::TopkSrc s{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, src_d, nullptr, flip};
+  return latency_run(1, path < 0 || nrows < kSmallTable ? default_path(1, nrows, k, nq) : path, s, nq, nrows, k,
+                     TopkScratch{scratch_d, scratch_i}, out_d_host, out_i_host, done_host, stream);
 }
 
 extern "C" int jb_topk_scores_direct(const float* src_d, int flip, int nq, int64_t nrows, int k,

@@ -99,7 +99,7 @@ _SIGS = {
     "jb_topk_mq_stats": (_i32, [_c_void_p]),
     "jb_topk_direct_scratch": (_i64, [_i32]),
     "jb_topk_scratch_init": (_i32, [_c_void_p, _c_void_p]),
-    "jb_topk_set_prof": (None, [_c_void_p]),
+    "jb_topk_default_path": (_i32, [_i32, _i64, _i32, _i32]),
     "jb_topk_direct_query_path": (_i32, [_c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p,
                                          _c_void_p, _i64, _i32, _i32, _i32, _i32, _c_void_p,
                                          _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32,
@@ -1495,6 +1495,21 @@ def _direct_scratch(nrows: int, k: int, nq: int) -> int:
 QUERY_SLOTS = 256      # kQuerySlots
 
 
+# paths of the latency top-k (csrc/hip/topk.hip TopkPath); the sampled path
+# is a default only, it cannot be forced
+TOPK_PATH_TILE, TOPK_PATH_CHAIN, TOPK_PATH_GRID_BARRIER, TOPK_PATH_SELECT, TOPK_PATH_SAMPLED = 0, 1, 2, 4, 5
+
+
+def topk_default_path(mode: int, nrows: int, k: int, nq: int) -> int:
+    """the TOPK_PATH_* a latency top-k call takes when no path is forced
+    (mode 0: signatures, topk_rows_direct / lsh_query_direct; mode 1: score
+    vectors, topk_scores_direct / pool_query_direct). Launches nothing."""
+    path = _fn("jb_topk_default_path")(mode, nrows, k, nq)
+    if path < 0:
+        raise ValueError("topk_default_path: mode / nrows / k / nq out of range")
+    return int(path)
+
+
 class DirectQueryBuffers:
     """pinned host outputs + device scratch of the LSH latency path"""
 
@@ -1536,10 +1551,11 @@ def lsh_query_direct(idx_ptr: int, val_ptr: int, row_ptr_ptr: int, nq: int, hash
 def topk_scores_direct(scores, nq: int, nrows: int, k: int, flip: bool,
                        bufs: DirectQueryBuffers, path: int = -1):
     """exact top-k smallest of a [nq, nrows] score matrix (flip: 1 - score)
-    -> (dist [nq, k], row [nq, k]) numpy; sampled threshold + collect + final
-    merge written to pinned host memory and waited for (csrc/hip/topk.hip
-    jb_topk_scores_direct; path >= 0 forces a path: 0 tile, 1 radix chain,
-    2 one launch with grid barriers, 3 one pass, k <= 16)"""
+    -> (dist [nq, k], row [nq, k]) numpy, written to pinned host memory and
+    waited for (csrc/hip/topk.hip jb_topk_scores_direct). path < 0: the
+    default, topk_default_path(1, ...); else forced: TOPK_PATH_TILE,
+    TOPK_PATH_CHAIN or TOPK_PATH_SELECT (tables under 16384 rows take the
+    tile path regardless); any other value raises (code -2)"""
     import numpy as np
     if not (0 < k <= TOPK_MAX_K and 0 < nq <= QUERY_MAX):
         raise ValueError("topk_scores_direct: k / nq out of range")
@@ -1611,9 +1627,10 @@ def lsh_set_rows_direct(idx_ptr: int, val_ptr: int, row_ptr_ptr: int, n: int, sl
 def topk_rows_direct(qbits, qnorm, nq: int, tbits, tnorm, valid, nrows: int, hash_num: int,
                      metric: int, k: int, bufs: DirectQueryBuffers, path: int = -1):
     """queries whose signatures are device rows (gathered table rows): fused
-    scan/top-k straight into pinned host memory -> numpy (dist, row) or None
-    (path >= 0 forces a path: 0 tile, 2 one launch with grid barriers, 3 one
-    pass, k <= 16)"""
+    scan/top-k straight into pinned host memory -> numpy (dist, row) or None.
+    path < 0: the default, topk_default_path(0, ...); else forced:
+    TOPK_PATH_TILE, TOPK_PATH_GRID_BARRIER or TOPK_PATH_SELECT; any other
+    value raises (code -2)"""
     import numpy as np
     words = (hash_num + 63) // 64
     if not (0 < k <= TOPK_MAX_K and words <= TOPK_MAX_WORDS and 0 < nq <= QUERY_MAX):

@@ -503,22 +503,19 @@ def test_topk_16_wave_path_matches_full_sort(k):
                                               ("random", 10, 3, 0), ("ties", 10, 2, 1),
                                               ("ties", 100, 1, 1), ("sparse_valid", 20, 2, 1),
                                               ("levels", 10, 4, 0), ("levels", 31, 2, 2)])
-@pytest.mark.parametrize("path", [-1, 2, 3, 4])
+@pytest.mark.parametrize("path", [-1, 2, 4])
 def test_direct_topk_one_launch_path(case, k, nq, metric, path):
     """latency top-k below the sampled path's 2M rows: ONE launch
     (csrc/hip/topk.hip topk_fused_kernel: distances cached in LDS, two radix
     levels across grid barriers, last-block selection) == full distance
-    matrix + stable sort; also the default choice (-1) and the one-pass
-    kernel (3, topk_onepass_kernel: register lists, last-block merge; k <= 16
-    only) and the LDS radix-select kernel (4, topk_select_kernel: per-block
+    matrix + stable sort; also the default choice (-1)
+    and the LDS radix-select kernel (4, topk_select_kernel: per-block
     exact top-k over (distance, row) composites, last-block select). "ties" (every row at one distance: the candidates
     overflow the LDS ranking and k > 16 retries on the tile path, k <= 16
     selects from L2), "levels" (8 distinct signatures: ~125k rows per
     distance level) and "sparse_valid" (fewer valid rows than k)"""
     import torch
     from jubatus_amd.ops import hip
-    if path == 3 and k > 16:
-        pytest.skip("the one-pass kernel takes k <= 16")
     d = dev()
     n = 1_000_000
     g = torch.Generator().manual_seed(k + nq + len(case) + metric)
@@ -551,6 +548,48 @@ def test_direct_topk_one_launch_path(case, k, nq, metric, path):
             np.testing.assert_array_equal(oi[q][:fin.sum()], order[fin])
             np.testing.assert_allclose(od[q][:fin.sum()], ref[fin], rtol=1e-6)
             assert np.all(np.isinf(od[q][fin.sum():]))
+
+
+def test_topk_default_path_table():
+    """the path a latency top-k takes when none is forced (csrc/hip/topk.hip
+    default_path), at both sides of every threshold; launches nothing"""
+    from jubatus_amd.ops import hip
+    tile, chain, barrier, select, sampled = (hip.TOPK_PATH_TILE, hip.TOPK_PATH_CHAIN, hip.TOPK_PATH_GRID_BARRIER,
+                                             hip.TOPK_PATH_SELECT, hip.TOPK_PATH_SAMPLED)
+    signatures = [(10_000, 100, 1, tile), (16_383, 31, 1, tile), (100_000, 10, 1, tile),
+                  (100_000, 10, 4, select), (262_144, 16, 2, select), (262_145, 16, 2, tile),
+                  (1_000_000, 10, 1, tile), (1_000_000, 10, 8, tile), (1_000_000, 17, 1, select),
+                  (1_000_000, 31, 1, select), (1_000_000, 67, 1, select),   # 67 000 000 <= 2^26
+                  (1_000_000, 68, 1, barrier), (1_000_000, 100, 2, barrier), (2_097_151, 10, 1, tile),
+                  (2_097_151, 128, 1, barrier), (2_097_152, 1, 1, sampled), (2_097_152, 128, 1, sampled),
+                  (2_200_000, 10, 2, sampled), (10_000_000, 128, 8, sampled)]
+    scores = [(16_383, 10, 1, tile), (16_384, 10, 1, select), (200_000, 100, 1, select),
+              (200_000, 10, 3, chain), (16_384, 128, 8, chain)]
+    assert len({tile, chain, barrier, select, sampled}) == 5
+    for mode, table in ((0, signatures), (1, scores)):
+        for nrows, k, nq, path in table:
+            assert hip.topk_default_path(mode, nrows, k, nq) == path, (mode, nrows, k, nq)
+
+
+@pytest.mark.parametrize("mode,path", [(0, 3), (1, 3), (1, 2)])
+def test_topk_retired_forced_path_is_an_error(mode, path):
+    """a forced path that no longer exists (3 the one-pass kernel, scores 2
+    the grid-barrier kernel on score vectors) is refused with code -2 before
+    anything is launched"""
+    import torch
+    from jubatus_amd.ops import hip
+    d = dev()
+    n, k = 200_000, 10
+    bufs = hip.DirectQueryBuffers(d, 1)
+    with pytest.raises(RuntimeError, match=r"code -2\b"):
+        if mode == 0:
+            tb = torch.zeros((n, 1), dtype=torch.int64, device=d)
+            tn = torch.ones(n, dtype=torch.float32, device=d)
+            valid = torch.ones(n, dtype=torch.uint8, device=d)
+            hip.topk_rows_direct(tb[:1].clone(), tn[:1].clone(), 1, tb, tn, valid, n, 64, 0, k, bufs, path=path)
+        else:
+            hip.topk_scores_direct(torch.zeros((1, n), dtype=torch.float32, device=d), 1, n, k, True, bufs,
+                                   path=path)
 
 
 @pytest.mark.parametrize("n,k", [(1000, 100), (300, 7), (50, 64), (2000, 33)])

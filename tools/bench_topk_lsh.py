@@ -1,8 +1,10 @@
 """Latency of the signature-table top-k of the LSH latency path
 (csrc/hip/topk.hip jb_topk_direct_query_path) at 1M rows: tile path (scan +
 per-block top-k, then a merge of blocks x k candidates) vs one launch
-(topk_fused_kernel). Random 64-bit signatures, euclid_lsh (metric 1) and lsh
-(metric 0). Both paths must return the same rows. One JSON line per case."""
+(fused: topk_fused_kernel, grid barriers; select: topk_select_kernel) vs the
+default choice ("taken": the hip.TOPK_PATH_* it ran). Random 64-bit
+signatures, euclid_lsh (metric 1) and lsh (metric 0). All paths must return
+the same rows. One JSON line per case."""
 import argparse
 import json
 import os
@@ -32,11 +34,12 @@ def main():
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--cases", default="1:10,4:10,1:100", help="nq:k pairs")
-    ap.add_argument("--paths", default="tile,fused,onepass,select,default")
+    ap.add_argument("--paths", default="tile,fused,select,default")
     ap.add_argument("--metrics", default="1,0")
     a = ap.parse_args()
     cases = [tuple(int(x) for x in c.split(":")) for c in a.cases.split(",")]
-    paths = [p for p in (("tile", 0), ("fused", 2), ("onepass", 3), ("select", 4), ("default", -1))
+    paths = [p for p in (("tile", hip.TOPK_PATH_TILE), ("fused", hip.TOPK_PATH_GRID_BARRIER),
+                         ("select", hip.TOPK_PATH_SELECT), ("default", -1))
              if p[0] in a.paths.split(",")]
     d = torch.device("cuda", 0)
     n = a.rows
@@ -52,8 +55,6 @@ def main():
             t = tuple(x.to(d) for x in (qb, qn, tb, tn, valid))
             ref = None
             for name, path in paths:
-                if path == 3 and k > 16:
-                    continue
                 lat = []
                 for it in range(a.iters + 20):
                     t0 = time.perf_counter()
@@ -63,7 +64,7 @@ def main():
                 if ref is None:
                     ref = idx
                 print(json.dumps({"rows": n, "metric": metric, "nq": nq, "k": k, "path": name,
-                                  "fuse_rows": os.environ.get("JB_FUSE_ROWS", ""),
+                                  "taken": path if path >= 0 else hip.topk_default_path(0, n, k, nq),
                                   "p50_us": round(float(np.median(lat)), 1),
                                   "p90_us": round(float(np.percentile(lat, 90)), 1),
                                   "same_rows_as_tile": bool(np.array_equal(idx, ref)),

@@ -3,7 +3,8 @@ jb_topk_scores_direct_path, the inverted-index recommender / LOF query
 tail) on synthetic score vectors: a fraction of rows with a nonzero cosine
 score (the rest 0, distance 1 after the flip), continuous or quantized
 (ties). Paths: tile (scan + merge), chain (radix hist / select x2, collect,
-rank: 6 launches + a memset), fused (one launch). Exactness against a
+rank: 6 launches + a memset), select (one launch, topk_select_kernel) and the
+default choice ("taken": the hip.TOPK_PATH_* it ran). Exactness against a
 stable (distance, row) sort. One JSON line per case."""
 import argparse
 import json
@@ -17,7 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from jubatus_amd.ops import hip  # noqa: E402
 
-PATHS = {"tile": 0, "chain": 1, "fused": 2, "onepass": 3, "select": 4, "default": -1}
+PATHS = {"tile": hip.TOPK_PATH_TILE, "chain": hip.TOPK_PATH_CHAIN, "select": hip.TOPK_PATH_SELECT, "default": -1}
 
 
 def run(sc, nq, rows, k, path, bufs):
@@ -35,7 +36,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--iters", type=int, default=300)
-    ap.add_argument("--paths", default="chain,fused,onepass,default")
+    ap.add_argument("--paths", default="chain,select,default")
     a = ap.parse_args()
     d = torch.device("cuda", 0)
     bufs = hip.DirectQueryBuffers(d, 8)
@@ -52,8 +53,6 @@ def main():
                 dist_ref = (1.0 - sc).cpu().numpy()
                 ref_i = [np.lexsort((np.arange(a.rows), dist_ref[q]))[:k] for q in range(nq)]
                 for path in a.paths.split(","):
-                    if path == "onepass" and k > 16:
-                        continue
                     torch.cuda.synchronize()
                     lat = []
                     ok = True
@@ -66,6 +65,8 @@ def main():
                             ok &= all(np.array_equal(idx[q], ref_i[q]) for q in range(nq))
                     print(json.dumps({"rows": a.rows, "nq": nq, "k": k, "nonzero_frac": frac,
                                       "levels": levels, "path": path,
+                                      "taken": PATHS[path] if PATHS[path] >= 0
+                                      else hip.topk_default_path(1, a.rows, k, nq),
                                       "p50_us": round(float(np.median(lat)), 1),
                                       "p90_us": round(float(np.percentile(lat, 90)), 1),
                                       "exact": bool(ok)}), flush=True)

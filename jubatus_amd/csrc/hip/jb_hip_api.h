@@ -313,6 +313,18 @@ int jb_pool_append(const uint8_t* pack, int n, int64_t nnz, int64_t base, int64_
                    int32_t* r_len, double* r_n2, uint8_t* valid, int32_t* p_idx, float* p_val,
                    hipStream_t stream);
 
+// sparse_pool_wide.hip: up to 64 device-CSR queries per pass over the pool.
+// jb_pool_wide_qm: the query lanes (16 / 32 / 64) of a pass of nq queries with
+// nuniq distinct features, 0 when no wide pass holds them; the launcher and
+// the Python pass planner both ask it. jb_pool_scan_wide: -2 an argument out
+// of range, -3 jb_pool_wide_qm says 0 (nothing launched in either case).
+int jb_pool_wide_qm(int nq, int nuniq);
+int jb_pool_scan_wide(const int64_t* qptr, const int32_t* qidx, const float* qval,
+                      const double* qn2, int nq, int nuniq, const int64_t* r_off,
+                      const int32_t* r_len, const double* r_n2, const uint8_t* valid,
+                      int64_t nrows, const int32_t* p_idx, const float* p_val, int metric,
+                      float* out, hipStream_t stream);
+
 // stepper.hip
 int jb_stepper_error();
 int jb_stepper_prof(unsigned long long* out);

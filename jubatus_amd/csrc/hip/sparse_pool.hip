@@ -27,6 +27,13 @@
 // features most rows share) a feature-major postings list would touch most
 // of the pool anyway and its scattered accumulation costs random atomics; one
 // coalesced pass over the pool is the bandwidth-optimal plan.
+//
+// Batches of 9 or more device-CSR queries can take sparse_pool_wide.hip
+// instead: up to 64 queries per pass, one lane per (row, query), the same
+// scores bit for bit. models/similarity.py selects it (InvertedIndex._wide:
+// JUBATUS_POOL_WIDE = 0 / 1, else from 9 queries on over at most 100000 rows,
+// profiles/pool_wide_scan.md); stored-row queries and the kernel-argument
+// path stay here. jb_pool.hpp holds what the two files share.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,6 +41,7 @@
 
 #include "jb_device.hpp"
 #include "jb_hip_api.h"
+#include "jb_pool.hpp"
 
 namespace jb {
 
@@ -41,8 +49,6 @@ constexpr int kPoolMaxQ = 8;          // queries per pass
 constexpr int kPoolMaxQEntries = 4096;
 
 constexpr int kRowsMaxBlocks = 4096;
-
-__device__ __forceinline__ uint32_t pool_hash(int32_t f) { return (uint32_t)f * 0x9E3779B1u; }
 
 template <int CTRL>
 __device__ __forceinline__ double dpp_d(double v) {
@@ -52,8 +58,8 @@ __device__ __forceinline__ double dpp_d(double v) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
 
-// Query sources of the scan. DevQuery: a device CSR (qptr / qidx / qval /
-// qn2) or stored rows (qslots: their runs are read from the pool). ArgQuery:
+// Query sources of the scan. DevQuery (jb_pool.hpp): a device CSR (qptr / qidx /
+// qval / qn2) or stored rows (qslots: their runs are read from the pool). ArgQuery:
 // the latency path - up to kArgSlots normalized query entries (or up to 8
 // stored-row slots) travel in the kernel arguments, so a single query needs
 // no H2D copy at all.
@@ -65,22 +71,6 @@ struct alignas(16) PoolQArgs {
   double qn2[kPoolMaxQ];
   int32_t idx[kArgSlots];
   float val[kArgSlots];
-};
-
-struct DevQuery {
-  const int64_t* qptr;
-  const int32_t* qidx;
-  const float* qval;
-  const double* qn2;
-  const int32_t* qslots;
-  __device__ bool by_slot() const { return qslots != nullptr; }
-  __device__ int32_t slot(int q) const { return qslots[q]; }
-  __device__ int64_t start(int q) const { return qptr[q]; }
-  __device__ int64_t end(int q) const { return qptr[q + 1]; }
-  __device__ int64_t base() const { return qptr[0]; }
-  __device__ double norm2(int q) const { return qn2[q]; }
-  __device__ int32_t f(int64_t i) const { return qidx[i]; }
-  __device__ float v(int64_t i) const { return qval[i]; }
 };
 
 struct ArgQuery {
@@ -214,17 +204,7 @@ __device__ __forceinline__ void pool_rows_body(
 #pragma unroll
       for (int q = 0; q < QM; ++q) {
         if (q >= nq) break;
-        float o;
-        if (!live) {
-          o = metric == 0 ? -INFINITY : INFINITY;
-        } else if (metric == 0) {
-          const double den = sqrt(s_qn2[q]) * sqrt(b2);
-          o = den > 0.0 ? (float)(dot[q] / den) : 0.f;
-        } else {
-          // dot products and norms in double: the euclidean distance of a row
-          // to itself (|q|^2 + |r|^2 - 2 q.r) must cancel to ~0
-          o = (float)sqrt(fmax(0.0, s_qn2[q] + b2 - 2.0 * dot[q]));
-        }
+        const float o = pool_score(live, metric, dot[q], s_qn2[q], b2);
         out[(int64_t)q * nrows + r] = o;
       }
     }

@@ -488,6 +488,19 @@ def _rows_to_csr(rows) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     return rp, idx, val
 
 
+# The many-query scan (csrc/hip/sparse_pool_wide.hip) behind InvertedIndex's
+# batched queries. The pass planner is the default from POOL_WIDE_FROM queries
+# on, over at most POOL_WIDE_MAX_ROWS rows (profiles/pool_wide_scan.md: at
+# 100 K rows it wins from 9 queries on, on both data shapes; at 1 M rows it
+# is slower on shared features and the 8-query passes stay;
+# JUBATUS_POOL_WIDE = 0 / 1 overrides). POOL_WIDE_SCORE_FLOATS caps the
+# [count, nrows] fp32 score matrix of one pass at 256 MiB: 64 queries up to
+# 1 M rows, 6 at 10 M (where the 8-query passes take over) - not 2.5 GB.
+POOL_WIDE_FROM = 9
+POOL_WIDE_MAX_ROWS = 100000
+POOL_WIDE_SCORE_FLOATS = 1 << 26
+
+
 class DevicePool:
     """HBM row pool of the device inverted index (csrc/hip/sparse_pool.hip):
     append-only runs of (feature, value) plus per-slot offset / length /
@@ -656,8 +669,12 @@ class InvertedIndex:
     euclidean distance). On a GPU the rows live in an HBM pool updated in
     place (DevicePool, csrc/hip/sparse_pool.hip) and up to 8 queries are
     scored per pass over it, then the fused top-k (csrc/hip/topk.hip) picks
-    the k best; without a GPU the rows are sorted sparse vectors on the
-    host (the oracle)."""
+    the k best. A batch of CSR queries that _wide() selects (POOL_WIDE_FROM,
+    JUBATUS_POOL_WIDE) goes through the pass planner _wide_passes instead:
+    normalised and staged once, up to 64 queries per pass on
+    csrc/hip/sparse_pool_wide.hip. Stored-row queries (query_slots) and
+    batches of 8 or fewer stay on the 8-query kernel. Without a GPU the rows
+    are sorted sparse vectors on the host (the oracle)."""
 
     def __init__(self, euclid: bool = False, device: Any = None):
         self.euclid = euclid
@@ -742,6 +759,8 @@ class InvertedIndex:
             if r is not None:
                 return self._direct_pairs(r, similar)
         rp = np.asarray(row_ptr[:nq + 1], np.int64)
+        if self._wide(nq, nrows):
+            return self._query_wide(rp - rp[0], idx[rp[0]:rp[nq]], val[rp[0]:rp[nq]], nrows, k, similar)
         return self._query_batches(
             lambda a, b: self._queries_csr(rp[a:b + 1] - rp[a], idx[rp[a]:rp[b]], val[rp[a]:rp[b]]),
             nq, nrows, k, similar)
@@ -778,6 +797,94 @@ class InvertedIndex:
             raise ValueError("query batch has more than 4096 features")
         hip.pool_scan(qptr, qi, qv, qn2, nq, self.pool, nrows, metric, out, qtotal=total)
         return out
+
+    def _wide(self, n: int, nrows: int) -> bool:
+        """whether a batch of n CSR queries over nrows rows takes the pass
+        planner (wide scan, csrc/hip/sparse_pool_wide.hip) or the 8-query passes.
+        JUBATUS_POOL_WIDE, read per call: 0 never, 1 wherever a wide pass fits;
+        unset: from POOL_WIDE_FROM queries on, up to POOL_WIDE_MAX_ROWS rows
+        (profiles/pool_wide_scan.md)."""
+        from ..ops import hip
+        if n <= hip.POOL_MAX_Q:
+            return False
+        knob = os.environ.get("JUBATUS_POOL_WIDE")
+        if knob in ("0", "1"):
+            return knob == "1"
+        return n >= POOL_WIDE_FROM and nrows <= POOL_WIDE_MAX_ROWS
+
+    def _wide_passes(self, rp, idx, val, nrows: int):
+        """The pass planner: host query CSR (rp[0] = 0; may hold idx < 0 /
+        repeats) -> yields (device scores [count * nrows], count) pass by pass,
+        in query order. The batch is normalised once and copied with one H2D
+        into a tensor of its own (not the pool's stager ring, which the top-k
+        between two passes rewinds); a pass addresses its queries as a
+        sub-range of that CSR.
+        Queries join a pass in order while hip.pool_wide_qm(count, distinct
+        features) holds them and count * nrows stays within
+        POOL_WIDE_SCORE_FLOATS; a run of 8 or fewer (a tail, or queries with
+        too many distinct features for a wide pass) goes to hip.pool_scan."""
+        import torch
+        from .._native import native
+        from ..ops import hip
+        lens, qi, qv, qn2 = native().csr_normalize(rp, idx, val)
+        n = int(lens.size)
+        qptr = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(lens, out=qptr[1:])
+        feats = qi
+        if qi.size == 0:
+            qi, qv = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        # int64 | float64 | int32 | float32, so that every view is aligned
+        parts = (qptr, np.asarray(qn2, np.float64), qi, qv)
+        pack = torch.from_numpy(np.concatenate([p.view(np.uint8) for p in parts])).to(self.device)
+        ends = np.cumsum([p.nbytes for p in parts])
+        dptr, dn2 = pack[:ends[0]].view(torch.int64), pack[ends[0]:ends[1]].view(torch.float64)
+        di, dv = pack[ends[1]:ends[2]].view(torch.int32), pack[ends[2]:].view(torch.float32)
+        metric = 1 if self.euclid else 0
+        most = max(1, min(hip.POOL_WIDE_MAX_Q, POOL_WIDE_SCORE_FLOATS // nrows))
+
+        def fits(a, b):      # distinct features of queries [a, b) if one wide pass holds them
+            u = int(np.unique(feats[qptr[a]:qptr[b]]).size)
+            return u if hip.pool_wide_qm(b - a, u) else None
+
+        a = 0
+        while a < n:
+            # the longest run [a, a + count) one wide pass holds (a shorter run has
+            # no more features and no more lanes, so the fitting lengths are a prefix)
+            hi = min(n, a + most)
+            count, nuniq = hi - a, None
+            if count > hip.POOL_MAX_Q:
+                nuniq = fits(a, hi)
+                lo, ulo = a + hip.POOL_MAX_Q, None       # shorter runs go to pool_scan anyway
+                while nuniq is None and hi - lo > 1:
+                    mid = (lo + hi) // 2
+                    u = fits(a, mid)
+                    if u is None:
+                        hi = mid
+                    else:
+                        lo, ulo = mid, u
+                if nuniq is None:
+                    hi, nuniq = lo, ulo
+                count = hi - a
+            if nuniq is not None:
+                out = torch.empty(count * nrows, dtype=torch.float32, device=self.device)
+                hip.pool_scan_wide(dptr[a:], di, dv, dn2[a:], count, nuniq, self.pool, nrows, metric, out)
+            else:
+                count = min(n - a, hip.POOL_MAX_Q)
+                if qptr[a + count] - qptr[a] > hip.POOL_MAX_Q_ENTRIES:      # one query at a time
+                    count = 1
+                total = int(qptr[a + count] - qptr[a])
+                if total > hip.POOL_MAX_Q_ENTRIES:
+                    raise ValueError("query batch has more than 4096 features")
+                out = torch.empty(count * nrows, dtype=torch.float32, device=self.device)
+                hip.pool_scan(dptr[a:], di, dv, dn2[a:], count, self.pool, nrows, metric, out, qtotal=total)
+            yield out, count
+            a += count
+
+    def _query_wide(self, rp, idx, val, nrows: int, k: int, similar: bool):
+        res = []
+        for sc, count in self._wide_passes(rp, idx, val, nrows):
+            res += self._topk(sc, count, nrows, k, similar)
+        return res
 
     def _query_batches(self, make, n: int, nrows: int, k: int, similar: bool):
         from ..ops import hip
@@ -829,13 +936,20 @@ class InvertedIndex:
         """as query(), but the lists stay on the device: -> (dist float32
         [nq, kk], row int32 [nq, kk]) ascending in the distance view (1 -
         cosine / euclid), +inf padded (kk = k on the fused top-k, min(k, nrows)
-        past TOPK_MAX_K). POOL_MAX_Q queries per pass over the pool. GPU index,
+        past TOPK_MAX_K). POOL_MAX_Q queries per pass over the pool, or the pass
+        planner's up to POOL_WIDE_MAX_Q where _wide() selects it. GPU index,
         nrows > 0, k > 0 and at least one query."""
         if not (self.gpu and nrows > 0 and k > 0 and rows):
             raise ValueError("query_device: needs a device index, rows, queries and k > 0")
         import torch
         from ..ops import hip
         ds, rs = [], []
+        if self._wide(len(rows), nrows):
+            for sc, count in self._wide_passes(*_rows_to_csr(rows), nrows):
+                d, i = self._topk_device(sc, count, nrows, k)
+                ds.append(d)
+                rs.append(i)
+            return (ds[0], rs[0]) if len(ds) == 1 else (torch.cat(ds), torch.cat(rs))
         for b0 in range(0, len(rows), hip.POOL_MAX_Q):
             b1 = min(len(rows), b0 + hip.POOL_MAX_Q)
             q = self._queries_device(rows[b0:b1])
@@ -878,6 +992,8 @@ class InvertedIndex:
 
     def query(self, rows: list, nrows: int, k: int, similar: bool) -> list[list[tuple[int, float]]]:
         if self.gpu and nrows > 0 and k > 0:
+            if self._wide(len(rows), nrows):
+                return self._query_wide(*_rows_to_csr(rows), nrows, k, similar)
             return self._query_batches(lambda a, b: self._queries_device(rows[a:b]), len(rows),
                                        nrows, k, similar)
         res = []

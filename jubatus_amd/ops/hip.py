@@ -133,6 +133,10 @@ _SIGS = {
     "jb_pool_scan": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32,
                             _c_void_p, _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p,
                             _i32, _i32, _c_void_p, _c_void_p]),
+    "jb_pool_wide_qm": (_i32, [_i32, _i32]),
+    "jb_pool_scan_wide": (_i32, [_c_void_p, _c_void_p, _c_void_p, _c_void_p, _i32, _i32, _c_void_p,
+                                 _c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _i32,
+                                 _c_void_p, _c_void_p]),
     "jb_pool_append": (_i32, [_c_void_p, _i32, _i64, _i64, _c_void_p, _c_void_p, _c_void_p,
                               _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "jb_lof_add": (_i32, [_i32, _c_void_p, _c_void_p, _i32, _i32, _i32, _i64, _c_void_p, _c_void_p,
@@ -688,6 +692,46 @@ def pool_scan(qptr, qidx, qval, qn2, nq: int, pool, nrows: int, metric: int, out
                              _p(pool.p_idx), _p(pool.p_val), metric, pool.lanes_per_row(nq),
                              _p(out), _stream())
     _check(rc, "jb_pool_scan")
+
+
+POOL_WIDE_MAX_Q = 64        # csrc/hip/sparse_pool_wide.hip kWideMaxQ
+
+
+def pool_wide_qm(nq: int, nuniq: int) -> int:
+    """query lanes (16, 32 or 64) of a wide pass of nq queries with nuniq
+    distinct features between them, 0 when no wide pass holds them: the
+    capacity rule of csrc/hip/sparse_pool_wide.hip, asked by its launcher and
+    by the pass planner of models/similarity.py alike"""
+    if not (0 <= nq < 2**31 and 0 <= nuniq < 2**31):
+        return 0
+    return int(_fn("jb_pool_wide_qm")(nq, nuniq))
+
+
+def pool_scan_wide(qptr, qidx, qval, qn2, nq: int, nuniq: int, pool, nrows: int, metric: int,
+                   out) -> None:
+    """pool_scan for up to POOL_WIDE_MAX_Q device-CSR queries in one pass
+    (csrc/hip/sparse_pool_wide.hip). qptr [nq + 1] holds positions in qidx /
+    qval (a pass over part of a batch takes a slice of the batch's qptr and
+    qn2); ``nuniq`` = the distinct features of the nq queries, which sizes the
+    kernel's LDS table: pool_wide_qm(nq, nuniq) must not be 0."""
+    if not 0 < nq <= POOL_WIDE_MAX_Q:
+        raise ValueError("pool_scan_wide: 1..64 queries per pass")
+    if metric not in (0, 1) or nuniq < 0:
+        raise ValueError("pool_scan_wide: bad metric or feature count")
+    _dev(out, torch.float32, "out")
+    _dev(qptr, torch.int64, "qptr")
+    _dev(qidx, torch.int32, "qidx")
+    _dev(qval, torch.float32, "qval")
+    _dev(qn2, torch.float64, "qn2")
+    if out.numel() < nq * nrows or not 0 < nrows <= pool.cap_rows or qptr.numel() < nq + 1 or \
+            qn2.numel() < nq or qidx.numel() != qval.numel():
+        raise ValueError("pool_scan_wide: bad operand shapes")
+    if pool_wide_qm(nq, nuniq) == 0:
+        raise ValueError(f"pool_scan_wide: {nuniq} distinct features do not fit a pass of {nq} queries")
+    rc = _fn("jb_pool_scan_wide")(_p(qptr), _p(qidx), _p(qval), _p(qn2), nq, nuniq, _p(pool.r_off),
+                                  _p(pool.r_len), _p(pool.r_n2), _p(pool.valid), nrows,
+                                  _p(pool.p_idx), _p(pool.p_val), metric, _p(out), _stream())
+    _check(rc, "jb_pool_scan_wide")
 
 
 def pool_append(pack, n: int, nnz: int, base: int, pool) -> None:

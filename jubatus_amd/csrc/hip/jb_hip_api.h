@@ -358,6 +358,13 @@ int jb_topk_scores_direct(const float* src_d, int flip, int nq, int64_t nrows, i
                           int32_t* out_i_host, uint32_t* done_host, hipStream_t stream);
 int jb_topk_mq_stats(unsigned long long* out4);
 
+// topk_wide.hip
+int64_t jb_topk_wide_scratch_bytes(int nq, int64_t nrows, int k);
+int jb_topk_wide(int mode, const uint64_t* qbits, const float* qnorm, int nq, const uint64_t* tbits,
+                 const float* tnorm, const uint8_t* valid, int64_t nrows, int words, int hash_num,
+                 int metric, const float* src_d, int flip, int k, void* scratch, float* out_d,
+                 int32_t* out_i, hipStream_t stream);
+
 // train_batch.hip
 int64_t jb_train_batch_args_bytes();
 // 0 ok, 1 a launch helper refused its arguments, 2 a HIP runtime error

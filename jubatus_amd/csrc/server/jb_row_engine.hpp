@@ -53,6 +53,7 @@ using jb::srv::DevBuf;
 using jb::srv::PinBuf;
 
 constexpr int kTopMaxK = 128;        // csrc/hip/topk.hip kTopMaxK
+constexpr int kTopWideMaxK = 4096;   // csrc/hip/topk_wide.hip kTopWideMaxK
 constexpr int kQueryMax = 8;         // lsh.hip kQueryMax
 constexpr int kQuerySlots = 256;     // lsh.hip kQuerySlots (direct paths)
 constexpr int kPoolMaxQ = 8;          // sparse_pool.hip kPoolMaxQ (queries per pass)
@@ -257,6 +258,12 @@ struct QueryBufs {
   DevBuf<float> sd;
   DevBuf<int32_t> si;
   DevBuf<float> scores;
+  // wide_topk: scratch and lists on the device, the lists in pinned host memory
+  DevBuf<uint64_t> wide;
+  DevBuf<float> wide_d;
+  DevBuf<int32_t> wide_i;
+  jb::srv::PinBuf<float> wide_hd;
+  jb::srv::PinBuf<int32_t> wide_hi;
   void init() {
     out_d = (float*)jb_host_alloc((int64_t)kQueryMax * kTopMaxK * 4);
     out_i = (int32_t*)jb_host_alloc((int64_t)kQueryMax * kTopMaxK * 4);
@@ -289,7 +296,30 @@ inline std::vector<Hit> direct_hits(const QueryBufs& b, int q, int k) {
   return out;
 }
 
-// exact top-k of a full host distance vector (k beyond the fused kernel)
+// One query's list of kTopMaxK < k <= kTopWideMaxK entries: selected on the
+// device (csrc/hip/topk_wide.hip; operands as jb_topk's), then k entries
+// copied back, not nrows.
+inline std::vector<Hit> wide_topk(QueryBufs& b, int mode, const uint64_t* qb, const float* qn,
+                                  const uint64_t* tbits, const float* tnorm, const uint8_t* valid,
+                                  int64_t nrows, int words, int hash_num, int metric, const float* scores,
+                                  int flip, int k, hipStream_t stream) {
+  uint64_t* scratch = b.wide.get((size_t)(jb_topk_wide_scratch_bytes(1, nrows, k) + 7) / 8);
+  float* dd = b.wide_d.get((size_t)k);
+  int32_t* di = b.wide_i.get((size_t)k);
+  const int rc = jb_topk_wide(mode, qb, qn, 1, tbits, tnorm, valid, nrows, words, hash_num, metric, scores,
+                              flip, k, scratch, dd, di, stream);
+  if (rc != 0) throw std::runtime_error("wide top-k failed: " + std::to_string(rc));
+  float* hd = b.wide_hd.get((size_t)k);
+  int32_t* hi = b.wide_hi.get((size_t)k);
+  HIPCHK(hipMemcpyAsync(hd, dd, 4 * (size_t)k, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(hi, di, 4 * (size_t)k, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  std::vector<Hit> out;
+  for (int j = 0; j < k && std::isfinite(hd[j]); ++j) out.push_back({hi[j], hd[j]});
+  return out;
+}
+
+// exact top-k of a full host distance vector (k beyond kTopWideMaxK)
 inline std::vector<Hit> host_topk(const std::vector<float>& d, int k) {
   std::vector<Hit> all;
   for (size_t i = 0; i < d.size(); ++i)
@@ -558,6 +588,9 @@ class LshIndex {
       if (rc != 0) throw std::runtime_error("lsh top-k failed: " + std::to_string(rc));
       return direct_hits(bufs_, 0, k);
     }
+    if (k <= kTopWideMaxK && words_ <= 16)
+      return wide_topk(bufs_, 0, qb, qn, (const uint64_t*)bits_.p, norms_.p, valid_.p, nrows, words_,
+                       hash_num_, metric_, nullptr, 0, k, stream_);
     float* out = bufs_.scores.get((size_t)nrows);
     const int rc = jb_hamming_scan(qb, qn, 1, (const uint64_t*)bits_.p, norms_.p, valid_.p, nrows, words_,
                                    hash_num_, metric_, out, stream_);
@@ -872,6 +905,9 @@ class PoolIndex {
 
   // scores (cosine similarity / euclidean distance) -> k smallest distances
   std::vector<Hit> scores_topk(const float* scores, int64_t nrows, int k) {
+    if (k > kTopMaxK && k <= kTopWideMaxK)
+      return wide_topk(bufs_, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nrows, 0, 0, 0, scores,
+                       euclid_ ? 0 : 1, k, stream_);
     std::vector<float> h((size_t)nrows);
     HIPCHK(hipMemcpyAsync(h.data(), scores, 4 * (size_t)nrows, hipMemcpyDeviceToHost, stream_));
     HIPCHK(hipStreamSynchronize(stream_));

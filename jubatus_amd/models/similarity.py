@@ -285,8 +285,8 @@ class LshIndex:
     def query(self, rows: list, nrows: int, k: int, similar: bool) -> list[list[tuple[int, float]]]:
         if self.gpu and nrows > 0 and rows:
             from ..ops import hip
-            if 0 < k <= hip.TOPK_MAX_K and self.words <= hip.TOPK_MAX_WORDS:
-                # fused scan + exact top-k (csrc/hip/topk.hip): no nq x N matrix
+            if hip.topk_on_device(k, len(rows)) and self.words <= hip.TOPK_MAX_WORDS:
+                # fused scan + exact top-k (csrc/hip/topk.hip, topk_wide.hip): no nq x N matrix
                 qb, qn = self._signatures(rows)
                 d, i = hip.topk_hamming(qb.contiguous(), qn.contiguous(), len(rows), self.bits,
                                         self.norms, self.valid, nrows, self.hash_num,
@@ -298,13 +298,14 @@ class LshIndex:
     def query_device(self, rows: list, nrows: int, k: int):
         """as query(), but the lists stay on the device: -> (dist float32
         [nq, kk], row int32 [nq, kk]) ascending, +inf padded (kk = k on the
-        fused top-k, min(k, nrows) past TOPK_MAX_K). GPU index, nrows > 0,
-        k > 0 and at least one query."""
+        fused top-k, that is hip.topk_on_device(k, nq) and hash_num <= 1024;
+        min(k, nrows) otherwise). GPU index, nrows > 0, k > 0 and at least
+        one query."""
         if not (self.gpu and nrows > 0 and k > 0 and rows):
             raise ValueError("query_device: needs a device index, rows, queries and k > 0")
         import torch
         from ..ops import hip
-        if k <= hip.TOPK_MAX_K and self.words <= hip.TOPK_MAX_WORDS:
+        if hip.topk_on_device(k, len(rows)) and self.words <= hip.TOPK_MAX_WORDS:
             qb, qn = self._signatures(rows)
             return hip.topk_hamming(qb.contiguous(), qn.contiguous(), len(rows), self.bits,
                                     self.norms, self.valid, nrows, self.hash_num, self.metric, k)
@@ -341,11 +342,11 @@ class LshIndex:
         if not (self.gpu and nrows > 0 and slots):
             return None
         from ..ops import hip
-        if not (0 < k <= hip.TOPK_MAX_K and self.words <= hip.TOPK_MAX_WORDS):
+        if not (hip.topk_on_device(k, len(slots)) and self.words <= hip.TOPK_MAX_WORDS):
             return None
         import torch
         slots = list(slots)
-        if len(slots) <= hip.QUERY_MAX:
+        if len(slots) <= hip.QUERY_MAX and k <= hip.TOPK_MAX_K:
             # latency path: rows gathered on the device, result in pinned host memory
             if self._direct is None:
                 self._direct = hip.DirectQueryBuffers(self.device, self.words)
@@ -909,9 +910,9 @@ class InvertedIndex:
             if similar:
                 out = [[(j, float(-dd if self.euclid else 1.0 - dd)) for j, dd in r] for r in out]
             return out
-        if k <= hip.TOPK_MAX_K:
+        if hip.topk_on_device(k, nq):
             d, i = hip.topk_scores(sc, nq, nrows, k, flip=not self.euclid)
-        else:       # wider than the fused top-k: torch.topk on the score matrix
+        else:       # past the device top-k: torch.topk on the score matrix
             import torch
             m = sc.view(nq, nrows)
             dist = m if self.euclid else (1.0 - m).nan_to_num(posinf=math.inf)
@@ -922,12 +923,14 @@ class InvertedIndex:
             out = [[(j, float(-dd if self.euclid else 1.0 - dd)) for j, dd in r] for r in out]
         return out
 
-    def _topk_device(self, sc, nq: int, nrows: int, k: int):
+    def _topk_device(self, sc, nq: int, nrows: int, k: int, total: int):
+        """lists of one pass (nq of the call's `total` queries; the call, not
+        the pass, picks the path: every pass returns the same width)"""
         import torch
         from ..ops import hip
-        if k <= hip.TOPK_MAX_K:
+        if hip.topk_on_device(k, total):
             return hip.topk_scores(sc, nq, nrows, k, flip=not self.euclid)
-        m = sc.view(nq, nrows)      # wider than the fused top-k: torch.topk on the score matrix
+        m = sc.view(nq, nrows)      # past the device top-k: torch.topk on the score matrix
         dist = m if self.euclid else (1.0 - m).nan_to_num(posinf=math.inf)
         d, i = torch.topk(dist, min(k, nrows), dim=1, largest=False, sorted=True)
         return d.contiguous(), i.to(torch.int32).contiguous()
@@ -935,8 +938,8 @@ class InvertedIndex:
     def query_device(self, rows: list, nrows: int, k: int):
         """as query(), but the lists stay on the device: -> (dist float32
         [nq, kk], row int32 [nq, kk]) ascending in the distance view (1 -
-        cosine / euclid), +inf padded (kk = k on the fused top-k, min(k, nrows)
-        past TOPK_MAX_K). POOL_MAX_Q queries per pass over the pool, or the pass
+        cosine / euclid), +inf padded (kk = k where hip.topk_on_device(k, nq),
+        min(k, nrows) otherwise). POOL_MAX_Q queries per pass over the pool, or the pass
         planner's up to POOL_WIDE_MAX_Q where _wide() selects it. GPU index,
         nrows > 0, k > 0 and at least one query."""
         if not (self.gpu and nrows > 0 and k > 0 and rows):
@@ -946,7 +949,7 @@ class InvertedIndex:
         ds, rs = [], []
         if self._wide(len(rows), nrows):
             for sc, count in self._wide_passes(*_rows_to_csr(rows), nrows):
-                d, i = self._topk_device(sc, count, nrows, k)
+                d, i = self._topk_device(sc, count, nrows, k, len(rows))
                 ds.append(d)
                 rs.append(i)
             return (ds[0], rs[0]) if len(ds) == 1 else (torch.cat(ds), torch.cat(rs))
@@ -958,7 +961,7 @@ class InvertedIndex:
             else:
                 parts = [(q, b1 - b0)]
             for qq, n in parts:
-                d, i = self._topk_device(self._scan(qq, n, nrows), n, nrows, k)
+                d, i = self._topk_device(self._scan(qq, n, nrows), n, nrows, k, len(rows))
                 ds.append(d)
                 rs.append(i)
         if len(ds) == 1:

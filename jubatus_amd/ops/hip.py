@@ -96,6 +96,10 @@ _SIGS = {
     "jb_nn_vote": (_i32, [_c_void_p, _c_void_p, _i32, _i32, _c_void_p, _i32, _i32, _i32, _f32,
                           _c_void_p, _c_void_p]),
     "jb_topk_blocks": (_i32, [_i64, _i32]),
+    "jb_topk_wide_scratch_bytes": (_i64, [_i32, _i64, _i32]),
+    "jb_topk_wide": (_i32, [_i32, _c_void_p, _c_void_p, _i32, _c_void_p, _c_void_p, _c_void_p, _i64,
+                            _i32, _i32, _i32, _c_void_p, _i32, _i32, _c_void_p, _c_void_p, _c_void_p,
+                            _c_void_p]),
     "jb_topk_mq_stats": (_i32, [_c_void_p]),
     "jb_topk_direct_scratch": (_i64, [_i32]),
     "jb_topk_scratch_init": (_i32, [_c_void_p, _c_void_p]),
@@ -518,8 +522,19 @@ def hamming_scan(qbits, qnorm, nq: int, tbits, tnorm, valid, nrows: int, hash_nu
     _check(rc, "jb_hamming_scan")
 
 
-TOPK_MAX_K = 128            # csrc/hip/topk.hip kTopMaxK
+TOPK_MAX_K = 128            # csrc/hip/topk.hip kTopMaxK: the pinned latency buffers and the direct paths
+TOPK_WIDE_MAX_K = 4096      # csrc/hip/topk_wide.hip kTopWideMaxK: topk_hamming / topk_scores past TOPK_MAX_K
 TOPK_MAX_WORDS = 16
+# queries a driver sends to topk_wide.hip in one call: with two or more the
+# chain re-reads the table per query and measured slower than the distance
+# matrix + torch.topk on most shapes (profiles/topk_wide.md)
+TOPK_WIDE_MAX_Q = 1
+
+
+def topk_on_device(k: int, nq: int) -> bool:
+    """whether the drivers (models/similarity.py) take topk_hamming /
+    topk_scores for nq lists of k entries"""
+    return 0 < k <= TOPK_MAX_K or (0 < k <= TOPK_WIDE_MAX_K and nq <= TOPK_WIDE_MAX_Q)
 
 
 def _topk_scratch(device, n: int):
@@ -541,10 +556,11 @@ _scratch: dict = {}
 
 def topk_hamming(qbits, qnorm, nq: int, tbits, tnorm, valid, nrows: int, hash_num: int,
                  metric: int, k: int):
-    """Fused signature scan + exact top-k (csrc/hip/topk.hip): -> (dist [nq, k],
-    row [nq, k]) device tensors, +inf / INT_MAX padded."""
+    """Fused signature scan + exact top-k (csrc/hip/topk.hip; k past TOPK_MAX_K:
+    topk_wide.hip): -> (dist [nq, k], row [nq, k]) device tensors, +inf /
+    INT_MAX padded."""
     words = (hash_num + 63) // 64
-    if not 0 < k <= TOPK_MAX_K or words > TOPK_MAX_WORDS:
+    if not 0 < k <= TOPK_WIDE_MAX_K or words > TOPK_MAX_WORDS:
         raise ValueError("topk_hamming: k or hash_num out of range")
     _dev(valid, torch.uint8, "valid")
     _dev(tnorm, torch.float32, "tnorm")
@@ -558,8 +574,8 @@ def topk_hamming(qbits, qnorm, nq: int, tbits, tnorm, valid, nrows: int, hash_nu
 
 def topk_scores(scores, nq: int, nrows: int, k: int, flip: bool):
     """Exact top-k smallest of a [nq, nrows] fp32 distance (flip: 1 - score)
-    matrix -> (dist [nq, k], row [nq, k])."""
-    if not 0 < k <= TOPK_MAX_K:
+    matrix -> (dist [nq, k], row [nq, k]); k up to TOPK_WIDE_MAX_K."""
+    if not 0 < k <= TOPK_WIDE_MAX_K:
         raise ValueError("topk_scores: k out of range")
     _dev(scores, torch.float32, "scores")
     if scores.numel() < nq * nrows:
@@ -578,6 +594,9 @@ def topk_mq_stats() -> list:
 
 def _topk(mode, qbits, qnorm, nq, tbits, tnorm, valid, nrows, words, hash_num, metric, src, flip,
           k, device):
+    if k > TOPK_MAX_K:
+        return _topk_wide(mode, qbits, qnorm, nq, tbits, tnorm, valid, nrows, words, hash_num, metric,
+                          src, flip, k, device)
     blocks = _fn("jb_topk_blocks")(nrows, k)
     sd, si = _topk_scratch(device, nq * blocks * k)
     out_d = torch.empty((nq, k), dtype=torch.float32, device=device)
@@ -586,6 +605,25 @@ def _topk(mode, qbits, qnorm, nq, tbits, tnorm, valid, nrows, words, hash_num, m
                         words, hash_num, metric, _p(src), flip, k, _p(sd), _p(si), _p(out_d),
                         _p(out_i), _stream())
     _check(rc, "jb_topk")
+    return out_d, out_i
+
+
+def _topk_wide(mode, qbits, qnorm, nq, tbits, tnorm, valid, nrows, words, hash_num, metric, src,
+               flip, k, device):
+    """the histogram-select chain of csrc/hip/topk_wide.hip (TOPK_MAX_K < k <=
+    TOPK_WIDE_MAX_K), up to 65535 queries (the grid's second dimension, as
+    jb_topk's)"""
+    need = (_fn("jb_topk_wide_scratch_bytes")(nq, nrows, k) + 7) // 8
+    key = (str(device), "topk_wide")
+    buf = _scratch.get(key)
+    if buf is None or buf.numel() < need:
+        buf = _scratch[key] = torch.empty(max(need, 1 << 16), dtype=torch.int64, device=device)
+    out_d = torch.empty((nq, k), dtype=torch.float32, device=device)
+    out_i = torch.empty((nq, k), dtype=torch.int32, device=device)
+    rc = _fn("jb_topk_wide")(mode, _p(qbits), _p(qnorm), nq, _p(tbits), _p(tnorm), _p(valid), nrows,
+                             words, hash_num, metric, _p(src), flip, k, _p(buf), _p(out_d), _p(out_i),
+                             _stream())
+    _check(rc, "jb_topk_wide")
     return out_d, out_i
 
 

@@ -248,9 +248,9 @@ int jb_nn_vote(const float* dist, const int32_t* row, int nq, int k, const int32
                int nrows, int nlabels, int mode, float alpha, float* out, hipStream_t stream);
 
 // regression.hip
-// method: models/linear_oracle.py METHOD_IDS (Method of jb_linear.hpp). PA
-// launches regression_train_kernel, the other methods the templated
-// regression_train_m_kernel. C is the regularization weight (perceptron: the
+// method: models/linear_oracle.py METHOD_IDS (Method of jb_linear.hpp), all
+// seven on the one templated regression_train_kernel (PA with 64 slots of a
+// sample in registers, the others 256). C is the regularization weight (perceptron: the
 // learning rate). P: the precision table of CW / AROW / NHERD, null
 // otherwise. slot_scratch: as many floats as fval, for those three methods;
 // may be null when no sample has more than 256 slots.

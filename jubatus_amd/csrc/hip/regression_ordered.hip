@@ -30,28 +30,24 @@
 //             keeps (table position, x) in LDS; a skipped slot (idx < 0) has
 //             position -1.
 //  c. apply   after a barrier wave 0 applies the window's samples one after
-//             the other from LDS: lane j owns slots j, j + 64, ... as in
-//             regression_train_m_kernel, the sums are wave_sum, the step is
-//             regression_step, the target statistics ride in wave 0's
-//             registers as sequential fp32 sums. Increments are LDS float
-//             atomic adds, so an index repeated inside a sample counts per
-//             occurrence. Every occurrence's w step and P increment take the
-//             pre-sample P: the first 256 slots keep it in registers, the
-//             slots beyond read it before any P add of the sample is issued
-//             and park their increments per occurrence in LDS; a wave's LDS
-//             operations execute in program order.
+//             the other from LDS, every one by regression_sample
+//             (jb_regression.hpp) on LdsTables: a sample of at most 64 slots
+//             with one slot a lane and no loops, a wider one with the first
+//             256 slots in registers and its parked P increments per
+//             occurrence in LDS. The target statistics ride in wave 0's
+//             registers as sequential fp32 sums.
 //  d. store   after a barrier all waves write the occupied entries back to
 //             W / P and empty the table. The next window's gathers and the
 //             global path of (e) must see these stores: every wave drains
 //             its stores, barrier, one lane releases and acquires at agent
 //             scope, barrier; the tables are read with agent-scope loads
-//             (ld_agent_r), as the existing kernels do.
+//             (ld_agent), as the existing kernels do.
 //  e. wide    a single sample of more than win_slots occurrences is applied
-//             between two windows by wave 0 alone, directly on global memory,
-//             with the gather-compute-scatter of regression_train_m_kernel
-//             (one stream) and a drain. slot_scratch has that kernel's
-//             contract: one float per slot, needed by CW / AROW / NHERD for
-//             samples of more than 256 slots.
+//             between two windows by wave 0 alone, directly on global memory:
+//             regression_sample on one stream's GlobalTables. slot_scratch is
+//             one float per slot, needed by CW / AROW / NHERD for samples of
+//             more than 256 slots; without it such a sample applies nothing
+//             and leaves the statistics untouched (status 3).
 //
 // Home position of row index idx in a table of 2^bits entries (mirrored by
 // ops/hip.py regression_ordered_home):
@@ -92,245 +88,6 @@ static_assert(tab_entries(kWinSlots) == 8192, "load 0.5 at the default window");
 static_assert(lds_bytes(kWinSlots) + 256 <= 160 * 1024, "the window image must fit the CU's LDS");
 
 enum : int { kOk = 0, kErrProbe = 1, kErrRowPtr = 2, kErrScratch = 3 };
-
-template <int M>
-__device__ __forceinline__ bool ordered_step(float loss, float nrm, float var, float C, float* tau,
-                                             float* beta) {
-  if (M == PA) {                      // regression_train_kernel: sgn * min(C, loss) / ||x||^2
-    *beta = 0.f;
-    if (!(loss > 0.f) || !(nrm > 0.f)) return false;
-    *tau = fminf(C, loss) / nrm;
-    return true;
-  }
-  return regression_step<M>(loss, nrm, var, C, tau, beta);
-}
-
-// the target statistics take y; -> the loss and the sign of the error
-__device__ __forceinline__ float take_target(float y, float dot, float eps, float& sum, float& sq,
-                                             float& cnt, float* sgn) {
-  sum += y; sq += y * y; cnt += 1.f;
-  const float avg = sum / cnt;
-  const float sd = sqrtf(fmaxf(0.f, sq / cnt - avg * avg));
-  const float err = y - dot;
-  *sgn = err > 0.f ? 1.f : -1.f;
-  return *sgn * err - eps * sd;
-}
-
-// c. a sample of at most 64 slots, from LDS (wave 0): one slot a lane, no
-// loops (lds_sample below, cut down to its first chunk; the same arithmetic)
-template <int M>
-__device__ __forceinline__ void lds_sample_narrow(const int* s_pos, const float* s_x, float* s_w,
-                                                  float* s_p, int off, int n, float y, float C,
-                                                  float eps, int lane, float& sum, float& sq,
-                                                  float& cnt) {
-  constexpr bool COV = M >= CW;
-  float dot = 0.f, nrm = 0.f, var = 0.f;
-  int pos = -1;
-  float x = 0.f, p = 1.f;
-  if (lane < n) { pos = s_pos[off + lane]; x = s_x[off + lane]; }
-  if (pos >= 0) {
-    const float w = s_w[pos];
-    if (COV) p = s_p[pos];
-    const float x2 = x * x;
-    dot += x * w;
-    nrm += x2;
-    if (COV) var += x2 * (1.f / p);
-  }
-  dot = wave_sum(dot);
-  nrm = wave_sum(nrm);
-  if (COV) var = wave_sum(var);
-  float sgn;
-  const float loss = take_target(y, dot, eps, sum, sq, cnt, &sgn);
-  float tau = 0.f, beta = 0.f;
-  if (!ordered_step<M>(loss, nrm, var, C, &tau, &beta)) return;
-  const float coeff = sgn * tau;
-  if (pos < 0) return;
-  if (!COV) {
-    atomicAdd(s_w + pos, coeff * x);                       // per occurrence
-    return;
-  }
-  const float sv = 1.f / p;
-  atomicAdd(s_w + pos, coeff * sv * x);
-  atomicAdd(s_p + pos, dprec(M, beta, x, sv));
-}
-
-// c. one sample of the window of any width, from LDS (wave 0). off / n: its
-// occurrences in s_pos / s_x. The shape of regression_train_m_kernel: the first kRegSlots
-// slots keep position, x and the pre-sample P in registers between the gather
-// and the scatter (their LDS reads are all in flight together); a wider
-// sample's remaining slots step w first, while P is still as the sample found
-// it, and park their P increments in s_dp.
-template <int M>
-__device__ __forceinline__ void lds_sample(const int* s_pos, const float* s_x, float* s_w, float* s_p,
-                                           float* s_dp, int off, int n, float y, float C, float eps,
-                                           int lane, float& sum, float& sq, float& cnt) {
-  constexpr bool COV = M >= CW;
-  float dot = 0.f, nrm = 0.f, var = 0.f;
-  int rpos[kRegChunks];
-  float rx[kRegChunks], rp[kRegChunks];
-#pragma unroll
-  for (int c = 0; c < kRegChunks; ++c) {
-    rpos[c] = -1; rx[c] = 0.f; rp[c] = 1.f;
-    if (c * 64 < n) {
-      const int j = c * 64 + lane;
-      if (j < n) { rpos[c] = s_pos[off + j]; rx[c] = s_x[off + j]; }
-      if (rpos[c] >= 0) {
-        const float w = s_w[rpos[c]];
-        if (COV) rp[c] = s_p[rpos[c]];
-        const float x2 = rx[c] * rx[c];
-        dot += rx[c] * w;
-        nrm += x2;
-        if (COV) var += x2 * (1.f / rp[c]);
-      }
-    }
-  }
-  for (int j = kRegSlots + lane; j < n; j += 64) {
-    const int pos = s_pos[off + j];
-    if (pos < 0) continue;
-    const float x = s_x[off + j];
-    const float w = s_w[pos];
-    dot += x * w;
-    nrm += x * x;
-    if (COV) var += x * x * (1.f / s_p[pos]);
-  }
-  dot = wave_sum(dot);
-  nrm = wave_sum(nrm);
-  if (COV) var = wave_sum(var);
-  float sgn;
-  const float loss = take_target(y, dot, eps, sum, sq, cnt, &sgn);
-  float tau = 0.f, beta = 0.f;
-  if (!ordered_step<M>(loss, nrm, var, C, &tau, &beta)) return;
-  const float coeff = sgn * tau;
-  if (!COV) {
-#pragma unroll
-    for (int c = 0; c < kRegChunks; ++c)
-      if (rpos[c] >= 0) atomicAdd(s_w + rpos[c], coeff * rx[c]);   // per occurrence
-    for (int j = kRegSlots + lane; j < n; j += 64) {
-      const int pos = s_pos[off + j];
-      if (pos >= 0) atomicAdd(s_w + pos, coeff * s_x[off + j]);
-    }
-    return;
-  }
-  // 1. slots past the registers: every P read here is the pre-sample P (no P
-  //    add of this sample has been issued; a wave's LDS operations execute in
-  //    program order), the P increments are parked
-  for (int j = kRegSlots + lane; j < n; j += 64) {
-    const int pos = s_pos[off + j];
-    if (pos < 0) continue;
-    const float x = s_x[off + j];
-    const float sv = 1.f / s_p[pos];
-    atomicAdd(s_w + pos, coeff * sv * x);
-    s_dp[off + j] = dprec(M, beta, x, sv);
-  }
-  // 2. register slots, from the P they gathered
-#pragma unroll
-  for (int c = 0; c < kRegChunks; ++c) {
-    if (rpos[c] < 0) continue;
-    const float sv = 1.f / rp[c];
-    atomicAdd(s_w + rpos[c], coeff * sv * rx[c]);
-    atomicAdd(s_p + rpos[c], dprec(M, beta, rx[c], sv));
-  }
-  // 3. the parked increments
-  for (int j = kRegSlots + lane; j < n; j += 64) {
-    const int pos = s_pos[off + j];
-    if (pos >= 0) atomicAdd(s_p + pos, s_dp[off + j]);
-  }
-}
-
-// e. one sample on global memory (wave 0): regression_train_m_kernel's one-stream
-// body. -> false: CW / AROW / NHERD past the register slots without slot_scratch
-// (nothing applied, the statistics untouched)
-template <int M>
-__device__ __forceinline__ bool global_sample(const int32_t* __restrict__ fidx,
-                                              const float* __restrict__ fval, int64_t beg, int n,
-                                              float y, float* W, float* P, float* slot_scratch,
-                                              float C, float eps, int lane, float& sum, float& sq,
-                                              float& cnt) {
-  constexpr bool COV = M >= CW;
-  if (COV && n > kRegSlots && slot_scratch == nullptr) return false;
-  float dot = 0.f, nrm = 0.f, var = 0.f;
-  int32_t ri[kRegChunks];
-  float rx[kRegChunks], rp[kRegChunks];
-#pragma unroll
-  for (int c = 0; c < kRegChunks; ++c) {
-    ri[c] = -1; rx[c] = 0.f; rp[c] = 1.f;
-    if (c * 64 < n) {
-      const int j = c * 64 + lane;
-      if (j < n) { ri[c] = fidx[beg + j]; rx[c] = fval[beg + j]; }
-      // earlier adds of this wave are drained before the first table read
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (ri[c] >= 0) {
-        const float w = ld_agent_r(W + ri[c]);
-        if (COV) rp[c] = ld_agent_r(P + ri[c]);
-        const float x2 = rx[c] * rx[c];
-        dot += rx[c] * w;
-        nrm += x2;
-        if (COV) var += x2 * (1.f / rp[c]);
-      }
-    }
-  }
-  for (int base = kRegSlots; base < n; base += 64) {
-    const int j = base + lane;
-    if (j >= n) continue;
-    const int32_t idx = fidx[beg + j];
-    if (idx < 0) continue;
-    const float x = fval[beg + j];
-    const float w = ld_agent_r(W + idx);
-    dot += x * w;
-    nrm += x * x;
-    if (COV) var += x * x * (1.f / ld_agent_r(P + idx));
-  }
-  dot = wave_sum(dot);
-  nrm = wave_sum(nrm);
-  if (COV) var = wave_sum(var);
-  float sgn;
-  const float loss = take_target(y, dot, eps, sum, sq, cnt, &sgn);
-  float tau = 0.f, beta = 0.f;
-  if (!ordered_step<M>(loss, nrm, var, C, &tau, &beta)) return true;
-  const float coeff = sgn * tau;
-  if (!COV) {
-#pragma unroll
-    for (int c = 0; c < kRegChunks; ++c)
-      if (ri[c] >= 0) atomicAdd(W + ri[c], coeff * rx[c]);   // per occurrence
-    for (int base = kRegSlots; base < n; base += 64) {
-      const int j = base + lane;
-      if (j >= n) continue;
-      const int32_t idx = fidx[beg + j];
-      if (idx >= 0) atomicAdd(W + idx, coeff * fval[beg + j]);
-    }
-    return true;
-  }
-  // 1. slots past the registers: P is still as the sample found it
-  for (int base = kRegSlots; base < n; base += 64) {
-    const int j = base + lane;
-    if (j >= n) continue;
-    const int32_t idx = fidx[beg + j];
-    if (idx < 0) continue;
-    const float x = fval[beg + j];
-    const float sv = 1.f / ld_agent_r(P + idx);
-    atomicAdd(W + idx, coeff * sv * x);
-    slot_scratch[beg + j] = dprec(M, beta, x, sv);
-  }
-  // every P read of step 1 has returned (and every parked increment is
-  // written) before the first P add below is issued
-  if (n > kRegSlots) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  // 2. register slots
-#pragma unroll
-  for (int c = 0; c < kRegChunks; ++c) {
-    if (ri[c] < 0) continue;
-    const float sv = 1.f / rp[c];
-    atomicAdd(W + ri[c], coeff * sv * rx[c]);
-    atomicAdd(P + ri[c], dprec(M, beta, rx[c], sv));
-  }
-  // 3. the parked increments
-  for (int base = kRegSlots; base < n; base += 64) {
-    const int j = base + lane;
-    if (j >= n) continue;
-    const int32_t idx = fidx[beg + j];
-    if (idx >= 0) atomicAdd(P + idx, ld_agent_r(slot_scratch + beg + j));
-  }
-  return true;
-}
 
 // d. the stores of every wave are visible to every later agent-scope load of
 // this workgroup (uniform control flow: every thread calls it). -> the error
@@ -392,9 +149,13 @@ __global__ __launch_bounds__(kThreads) void regression_ordered_kernel(
       const int64_t wide = row_ptr[s + 1] - base;
       if (wide <= 0 || wide > INT32_MAX) { code = kErrRowPtr; break; }
       if (wave0) {
-        const bool ok = global_sample<M>(fidx, fval, base, (int)wide, targets[s], W, P, slot_scratch,
-                                         C, eps, lane, sum, sq, cnt);
-        if (!ok && lane == 0) s_err = kErrScratch;
+        if (COV && wide > kRegSlots && slot_scratch == nullptr) {
+          if (lane == 0) s_err = kErrScratch;
+        } else {
+          const float y = targets[s];
+          const GlobalTables<false> t{fidx, fval, base, W, P, slot_scratch};
+          regression_sample<M, kRegChunks, true>(t, (int)wide, &y, C, eps, lane, sum, sq, cnt);
+        }
       }
       const int err = publish_block(&s_err);
       if (err != kOk) { code = err; break; }
@@ -427,8 +188,8 @@ __global__ __launch_bounds__(kThreads) void regression_ordered_kernel(
     for (int t = tid; t < tab; t += kThreads) {
       const int key = s_key[t];
       if (key < 0) continue;
-      s_w[t] = ld_agent_r(W + key);
-      if (COV) s_p[t] = ld_agent_r(P + key);
+      s_w[t] = ld_agent(W + key);
+      if (COV) s_p[t] = ld_agent(P + key);
     }
     __syncthreads();
     // c. wave 0 applies the samples in order (none of them when the load failed;
@@ -451,10 +212,11 @@ __global__ __launch_bounds__(kThreads) void regression_ordered_kernel(
           const int off = __builtin_amdgcn_readlane((int)b, k);
           const int n = __builtin_amdgcn_readlane((int)en, k) - off;
           const float y = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tg), k));
+          const LdsTables t{s_pos, s_x, s_w, s_p, s_dp, off};
           if (n <= 64)
-            lds_sample_narrow<M>(s_pos, s_x, s_w, s_p, off, n, y, C, eps, lane, sum, sq, cnt);
+            regression_sample<M, 1, false>(t, n, &y, C, eps, lane, sum, sq, cnt);
           else
-            lds_sample<M>(s_pos, s_x, s_w, s_p, s_dp, off, n, y, C, eps, lane, sum, sq, cnt);
+            regression_sample<M, kRegChunks, true>(t, n, &y, C, eps, lane, sum, sq, cnt);
         }
         if (badm) {
           if (lane == 0) { s_err = kErrRowPtr; s_fail = (int)(blk + good - s); }
@@ -502,8 +264,8 @@ extern "C" int jb_regression_train_ordered(const int64_t* row_ptr, const int32_t
   int bits = 0;
   while ((1 << bits) < tab) ++bits;
   const int bytes = ord::lds_bytes(win);
-#define JB_ORD_LAUNCH(M)                                                                          \
-  case M: {                                                                                       \
+#define JB_ORDERED(M)                                                                             \
+  {                                                                                               \
     static const hipError_t attr = hipFuncSetAttribute(                                           \
         (const void*)jb::ord::regression_ordered_kernel<M>,                                       \
         hipFuncAttributeMaxDynamicSharedMemorySize, jb::ord::lds_bytes(jb::ord::kWinSlots));      \
@@ -511,17 +273,8 @@ extern "C" int jb_regression_train_ordered(const int64_t* row_ptr, const int32_t
     hipLaunchKernelGGL((jb::ord::regression_ordered_kernel<M>), dim3(1), dim3(jb::ord::kThreads), \
                        bytes, stream, row_ptr, fidx, fval, targets, n_samples, W, P, stats,       \
                        slot_scratch, C, eps, win, bits, status);                                  \
-    break;                                                                                        \
   }
-  switch (method) {
-    JB_ORD_LAUNCH(jb::PERCEPTRON)
-    JB_ORD_LAUNCH(jb::PA)
-    JB_ORD_LAUNCH(jb::PA1)
-    JB_ORD_LAUNCH(jb::PA2)
-    JB_ORD_LAUNCH(jb::CW)
-    JB_ORD_LAUNCH(jb::AROW)
-    JB_ORD_LAUNCH(jb::NHERD)
-  }
-#undef JB_ORD_LAUNCH
+  JB_REG_DISPATCH(method, JB_ORDERED)
+#undef JB_ORDERED
   return (int)hipGetLastError();
 }

@@ -1305,7 +1305,8 @@ def regression_train(row_ptr, fidx, fval, targets, stream_ptr, nstreams: int, W,
     AROW and NHERD take the precision table ``P`` (like W) and, for samples of
     more than 256 slots, ``slot_scratch`` (float32, as long as fval; without
     it the widths are checked here, which costs a device synchronisation).
-    The library launches PA's own kernel for PA."""
+    Every method runs the same kernel template; PA keeps 64 slots of a sample
+    in registers, the other methods 256."""
     from ..models.linear_oracle import METHOD_IDS, USES_COVARIANCE
     _dev(W, torch.float32, "W")
     _dev(stats, torch.float32, "stats")
